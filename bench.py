@@ -12,6 +12,12 @@ Extra knobs beyond the driver contract:
   --microbatches M      pipeline microbatches (default: 1 if N==1 else N/2)
   --slowdowns CSV       per-rank injected compute slowdown factors
   --stimulate           seeded synthetic heterogeneity for the allocator
+  --dump-outputs DIR    after the timed steps, write what the last timed step
+                        returned/updated as DIR/<name>.npy (float32)
+  --full                also run the benchmark's secondary measurements; a
+                        plain run does only setup, warmup, the timed steps
+                        and the result line (there are none today: the flag
+                        is accepted so callers can rely on it)
 """
 
 from __future__ import annotations
@@ -45,7 +51,38 @@ def parse_args():
     p.add_argument("--no-graph", action="store_true",
                    help="disable hipGraph step capture (1-GPU path)")
     p.add_argument("--json-out", default="")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements (none today)")
     return p.parse_args()
+
+
+_DUMP_PER_PARAM = 256  # sampled elements per parameter tensor
+
+
+def dump_outputs(dirname, loss, params):
+    """Write the arrays a caller of the timed step receives: the step's
+    returned loss and the parameters it updated in place. The parameters
+    are a fixed seeded sample (the full 160-layer model is ~8 GB in fp32):
+    _DUMP_PER_PARAM flat indices per tensor, drawn from a private generator
+    so the sample is identical from run to run and build to build."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    if loss is not None:
+        val = float(loss.detach().float().cpu()) if torch.is_tensor(loss) else float(loss)
+        np.save(os.path.join(dirname, "loss.npy"), np.asarray([val], dtype=np.float32))
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(0xD0)
+    chunks = []
+    for prm in params:
+        flat = prm.detach().reshape(-1)
+        idx = torch.randint(0, flat.numel(), (_DUMP_PER_PARAM,), generator=gen)
+        chunks.append(flat[idx.to(flat.device)].float().cpu())
+    if chunks:
+        np.save(os.path.join(dirname, "params_sample.npy"),
+                torch.cat(chunks).numpy().astype(np.float32))
 
 
 def main():
@@ -188,30 +225,41 @@ def main():
     def step(i):
         data, labels = batches[i % len(batches)]
         if graphed is not None:
-            graphed.step(data, labels)
-            return
+            return graphed.step(data, labels)
         opt.zero_grad(set_to_none=True)
         if virtual > 1:
-            engine.run_iteration(data, labels, num_microbatches=M)
+            loss = engine.run_iteration(data, labels, num_microbatches=M)
         else:
-            engine.run_iteration(data, labels, num_microbatches=M,
-                                 schedule=args.schedule)
+            loss = engine.run_iteration(data, labels, num_microbatches=M,
+                                        schedule=args.schedule)
         opt.step()
+        return loss
+
+    def barrier():
+        # a one-rank world has nobody to wait for, and the first device
+        # barrier would spend seconds creating an RCCL communicator that
+        # the single-GPU step never uses
+        if world > 1:
+            comm.barrier()
 
     for i in range(args.warmup):
         step(i)
-    comm.barrier()
+    barrier()
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_loss = None
     for i in range(args.steps):
-        step(i)
-    comm.barrier()
+        last_loss = step(i)
+    barrier()
     if use_cuda:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed = max(comm.all_gather_object(elapsed))
     sec_per_iter = elapsed / args.steps
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, list(engine.parameters()))
 
     if rank == 0:
         result = {

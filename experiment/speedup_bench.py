@@ -144,6 +144,14 @@ def main():
             with open(args.json_out, "w") as f:
                 f.write(line + "\n")
 
+    # tear the process groups down before interpreter exit: a rank that
+    # exits with them alive can abort in the c10d background threads
+    # ("terminate called without an active exception") on a loaded machine
+    comm.barrier()
+    from skycomputing_amd.parallel import destroy
+
+    destroy()
+
 
 if __name__ == "__main__":
     main()

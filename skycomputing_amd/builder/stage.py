@@ -97,9 +97,11 @@ class StageModule(nn.Module):
         else:
             self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.compute_dtype = dtype
-        self.to(self.device)
+        # cast on the host first: same round-to-nearest-even values, but a
+        # bf16 stage then crosses to the device with half the bytes
         if dtype is not None:
             self.module.to(dtype)
+        self.to(self.device)
 
     def _prep(self, args):
         out = []

@@ -40,6 +40,40 @@ def test_bench_json_contract(tmp_path):
     assert json.loads(out.read_text()) == d
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss and a fixed sample of
+    the updated parameters as float32 .npy files; same arguments give the
+    same arrays from run to run, and --full changes neither them nor the
+    single result line."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        env = dict(os.environ)
+        env["MASTER_PORT"] = str(21000 + (os.getpid() + 7) % 20000)
+        r = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--layers", "1",
+             "--batch", "8", "--seq", "16", "--steps", "2", "--warmup", "1",
+             "--dump-outputs", str(d), *extra],
+            cwd=REPO, env=env, capture_output=True, text=True, timeout=420,
+        )
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        json_lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(json_lines) == 1
+        res = json.loads(json_lines[0])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        assert sorted(p.name for p in d.iterdir()) == ["loss.npy", "params_sample.npy"]
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        for a in arrs.values():
+            assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+        assert arrs["loss"].shape == (1,)
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        dumps.append(arrs)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
+
+
 def _torchrun_bench(nproc, extra, out, attempts=3):
     """Run bench.py under torch.distributed.run; one retry on a fresh
     rendezvous port (loaded machines occasionally drop the first

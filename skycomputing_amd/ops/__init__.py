@@ -117,6 +117,8 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
     (FusedAttentionFn). Otherwise: strided-view batched GEMMs + fused
     masked softmax (HIP on GPU, eager on CPU)."""
+    from .functions import _split_heads
+
     B, S, three, h, d = qkv.shape
     scale = 1.0 / math.sqrt(d)
     if (
@@ -143,9 +145,7 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
         # do (S<=128 is the fused MFMA kernel above). Measured at S=512:
         # sdpa ~26 us core vs 108 us decomposed / 176 us flash-v1.
         if os.environ.get("SKY_NO_SDPA") != "1":
-            q = qkv[:, :, 0].permute(0, 2, 1, 3)
-            k = qkv[:, :, 1].permute(0, 2, 1, 3)
-            v = qkv[:, :, 2].permute(0, 2, 1, 3)
+            q, k, v = _split_heads(qkv)
             am = mask
             if am is not None:
                 am = am.to(qkv.dtype)  # additive [B,1,1,S], broadcast
@@ -154,9 +154,7 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
                 dropout_p=dropout_p if training else 0.0,
             )
             return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
-    q = qkv[:, :, 0].permute(0, 2, 1, 3)
-    k = qkv[:, :, 1].permute(0, 2, 1, 3)
-    v = qkv[:, :, 2].permute(0, 2, 1, 3)
+    q, k, v = _split_heads(qkv)
     ctx = attention_context(q, k, v, mask, dropout_p, training)
     return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
 

@@ -30,7 +30,7 @@ CFLAGS = [
 
 def _source_hash(sources: list[str]) -> str:
     h = hashlib.sha256()
-    for s in sorted(sources) + [os.path.join(HIP_DIR, "common.h")]:
+    for s in sorted(sources) + sorted(glob.glob(os.path.join(HIP_DIR, "*.h"))):
         with open(s, "rb") as f:
             h.update(f.read())
     h.update(" ".join(CFLAGS).encode())

@@ -263,13 +263,52 @@ class DropoutFn(torch.autograd.Function):
         return dx, None
 
 
+def _split_heads(qkv):
+    """q, k, v views [B, h, S, d] of a packed qkv [B, S, 3, h, d]."""
+    return tuple(qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+
+
+def _attn_bwd_decomposed(qkv, P, Pd, dout, scale, dP_of):
+    """Five-GEMM attention backward from materialized probabilities P and
+    their dropped-out copy Pd (both [B, h, S, S]); dP_of maps dPd to dP
+    with the caller's own way of regenerating the dropout mask. Returns
+    dqkv packed like qkv."""
+    lib = hiplib.require()
+    B, S, _, h, d = qkv.shape
+    q, k, v = _split_heads(qkv)
+    dO = dout.permute(0, 2, 1, 3).contiguous()  # one copy, used twice
+    dV = torch.matmul(Pd.transpose(-1, -2), dO)
+    dPd = torch.matmul(dO, v.transpose(-1, -2)).contiguous()
+    dP = dP_of(dPd)
+    dS = torch.empty_like(dP)
+    check(
+        lib.sky_masked_softmax_bwd(
+            _stream(), ptr(dP), ptr(P), ptr(dS), B, h, S, S, scale,
+            1.0, 0, _dt(P),
+        ),
+        "sky_masked_softmax_bwd",
+    )
+    dQ = torch.matmul(dS, k)                      # [B,h,S,d]
+    dK = torch.matmul(dS.transpose(-1, -2), q)    # [B,h,S,d]
+    dqkv = torch.empty_like(qkv)
+    check(
+        lib.sky_pack3(
+            _stream(), ptr(dQ.contiguous()), ptr(dK.contiguous()),
+            ptr(dV.contiguous()), ptr(dqkv), B, S, h, d, _dt(qkv),
+        ),
+        "sky_pack3",
+    )
+    return dqkv
+
+
 class FusedAttentionFn(torch.autograd.Function):
     """Fused attention: out = dropout(softmax(scale*QK^T + mask)) V in ONE
     MFMA kernel (ops/hip/attention.hip); S x S probabilities are never
     materialized in forward (row max/sum saved, flash-style).
 
-    Backward default: TWO fused MFMA kernels (sky_attn_bwd) — recompute +
-    dS + dQ, then dK/dV over transposed scratch — no torch ops at all.
+    Backward default: TWO fused MFMA kernels (sky_attn_bwd,
+    ops/hip/attention_bwd.hip) — recompute + dS + dQ, then dK/dV over
+    transposed scratch — no torch ops at all.
     SKY_NO_FUSED_ATTN_BWD=1 selects the decomposed fallback (sky_attn_probs
     recompute + hipBLASLt batched GEMMs + HIP softmax-backward).
 
@@ -325,9 +364,13 @@ class FusedAttentionFn(torch.autograd.Function):
                 )
                 return dqkv, None, None, None, None
             # two-kernel path (bwd1s + bwd2 over transposed scratch)
+            # scratch [B,h,S,S]. bwd2 loads whole 32-q fragments, so for
+            # S % 32 != 0 the last row's load runs past the tensor; zero
+            # B rows null it only if those bytes are finite -> zeroed tail
             alloc = torch.empty if S == 128 else torch.zeros
-            pdT = alloc((B, h, S, S), dtype=qkv.dtype, device=dev)
-            dsT = alloc((B, h, S, S), dtype=qkv.dtype, device=dev)
+            n = B * h * S * S + (32 if S % 32 else 0)
+            pdT = alloc(n, dtype=qkv.dtype, device=dev)
+            dsT = alloc(n, dtype=qkv.dtype, device=dev)
             check(
                 lib.sky_attn_bwd(
                     _stream(), ptr(qkv), ptr(dout), ptr(mask), ptr(m),
@@ -348,44 +391,24 @@ class FusedAttentionFn(torch.autograd.Function):
             ),
             "sky_attn_probs",
         )
-        dO = dout.permute(0, 2, 1, 3).contiguous()  # one copy, used twice
-        q = qkv[:, :, 0].permute(0, 2, 1, 3)
-        k = qkv[:, :, 1].permute(0, 2, 1, 3)
-        v = qkv[:, :, 2].permute(0, 2, 1, 3)
-        dV = torch.matmul(Pd.transpose(-1, -2), dO)
-        dPd = torch.matmul(dO, v.transpose(-1, -2)).contiguous()
-        if ctx.keep < 1.0:
-            # regenerate the dropout mask from Pd (zero where dropped; a
-            # P-underflow zero also zeroes dS, so no false positives matter)
-            dP = torch.where(
-                Pd != 0, dPd * (1.0 / ctx.keep), torch.zeros((), dtype=dPd.dtype, device=dPd.device)
-            )
-        else:
-            dP = dPd
-        dS = torch.empty_like(dP)
-        check(
-            lib.sky_masked_softmax_bwd(
-                _stream(), ptr(dP), ptr(P), ptr(dS), B, h, S, S, ctx.scale,
-                1.0, 0, _dt(P),
-            ),
-            "sky_masked_softmax_bwd",
-        )
-        dQ = torch.matmul(dS, k)                      # [B,h,S,d]
-        dK = torch.matmul(dS.transpose(-1, -2), q)    # [B,h,S,d]
-        dqkv = torch.empty_like(qkv)
-        check(
-            lib.sky_pack3(
-                _stream(), ptr(dQ.contiguous()), ptr(dK.contiguous()),
-                ptr(dV.contiguous()), ptr(dqkv), B, S, h, d, _dt(qkv),
-            ),
-            "sky_pack3",
-        )
+
+        def dP_of(dPd):
+            if ctx.keep < 1.0:
+                # regenerate the dropout mask from Pd (zero where dropped; a
+                # P-underflow zero also zeroes dS, so no false positives matter)
+                return torch.where(
+                    Pd != 0, dPd * (1.0 / ctx.keep), torch.zeros((), dtype=dPd.dtype, device=dPd.device)
+                )
+            return dPd
+
+        dqkv = _attn_bwd_decomposed(qkv, P, Pd, dout, ctx.scale, dP_of)
         return dqkv, None, None, None, None
 
 
 class FlashAttentionFn(torch.autograd.Function):
     """Flash-style attention for arbitrary S (d = 64, bf16): the forward is
-    one online-softmax MFMA kernel per (batch, head, 128-query block); the
+    one online-softmax MFMA kernel (ops/hip/attention_flash.hip) per
+    (batch, head, 128-query block); the
     S x S matrix never exists in forward. Backward recomputes probabilities
     (hipBLASLt scores GEMM + HIP masked-softmax) and regenerates the
     dropout mask from the saved salt (linear element indices match the
@@ -419,10 +442,7 @@ class FlashAttentionFn(torch.autograd.Function):
         lib = hiplib.require()
         qkv, mask = ctx.saved_tensors
         B, S, _, h, d = qkv.shape
-        dev = qkv.device
-        q = qkv[:, :, 0].permute(0, 2, 1, 3)
-        k = qkv[:, :, 1].permute(0, 2, 1, 3)
-        v = qkv[:, :, 2].permute(0, 2, 1, 3)
+        q, k, _ = _split_heads(qkv)
         scores = torch.matmul(q, k.transpose(-1, -2)).contiguous()
         P = torch.empty_like(scores)
         check(
@@ -443,38 +463,21 @@ class FlashAttentionFn(torch.autograd.Function):
             )
         else:
             Pd = P
-        dO = dout.permute(0, 2, 1, 3).contiguous()
-        dV = torch.matmul(Pd.transpose(-1, -2), dO)
-        dPd = torch.matmul(dO, v.transpose(-1, -2)).contiguous()
-        if ctx.keep < 1.0:
-            dP = torch.empty_like(dPd)
-            check(
-                lib.sky_dropout_bwd(
-                    _stream(), ptr(dPd), ptr(dP), dPd.numel(), ctx.keep,
-                    ctx.salt, rng_state().data_ptr(), _dt(dPd),
-                ),
-                "sky_dropout_bwd",
-            )
-        else:
-            dP = dPd
-        dS = torch.empty_like(dP)
-        check(
-            lib.sky_masked_softmax_bwd(
-                _stream(), ptr(dP), ptr(P), ptr(dS), B, h, S, S, ctx.scale,
-                1.0, 0, _dt(P),
-            ),
-            "sky_masked_softmax_bwd",
-        )
-        dQ = torch.matmul(dS, k)
-        dK = torch.matmul(dS.transpose(-1, -2), q)
-        dqkv = torch.empty_like(qkv)
-        check(
-            lib.sky_pack3(
-                _stream(), ptr(dQ.contiguous()), ptr(dK.contiguous()),
-                ptr(dV.contiguous()), ptr(dqkv), B, S, h, d, _dt(qkv),
-            ),
-            "sky_pack3",
-        )
+
+        def dP_of(dPd):
+            if ctx.keep < 1.0:
+                dP = torch.empty_like(dPd)
+                check(
+                    lib.sky_dropout_bwd(
+                        _stream(), ptr(dPd), ptr(dP), dPd.numel(), ctx.keep,
+                        ctx.salt, rng_state().data_ptr(), _dt(dPd),
+                    ),
+                    "sky_dropout_bwd",
+                )
+                return dP
+            return dPd
+
+        dqkv = _attn_bwd_decomposed(qkv, P, Pd, dout, ctx.scale, dP_of)
         return dqkv, None, None, None, None
 
 
@@ -611,8 +614,6 @@ def gemm2_fwd(x2, weight, bias=None, gelu=False, want_z=False):
         return None
     epi = 2 if gelu else (1 if bias is not None else 0)
     gsu = _g2_gsu(M, N, K)
-    if gsu > 1 and epi == 2 and want_z:
-        pass  # reduce kernel handles bias+gelu+z too
     y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
     z = torch.empty_like(y) if (gelu and want_z) else None
     _g2_call(x2, weight, y, bias, z, M, N, K, x2.stride(0), weight.stride(0),

@@ -1,0 +1,204 @@
+// Shared tile math of the attention kernels (attention.hip,
+// attention_bwd.hip, attention_flash.hip): types, LDS addressing and one
+// DEV helper per block the kernels have in common. All helpers assume the
+// kernels' lane split lm = lane & 15 (MFMA column), lg = lane >> 4 (row
+// group), 256-thread blocks, d = 64.
+#pragma once
+
+#include "common.h"
+
+typedef const __attribute__((address_space(1))) unsigned int* att_gas;
+typedef __attribute__((address_space(3))) unsigned int* att_las;
+
+typedef __attribute__((ext_vector_type(8))) short bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+#define ATT_SMAX 128
+#define ATT_D 64
+
+DEV void* lds_at(char* base, int byte) { return (void*)(base + byte); }
+
+DEV int swz(int byte_addr, int row, int rmask) {
+  return byte_addr ^ ((row & rmask) << 4);
+}
+
+typedef __attribute__((ext_vector_type(4))) short s16x4_a;
+typedef __attribute__((address_space(3))) s16x4_a* abf_las4;
+
+// tr16 read of an MFMA fragment from a row-major [row][64] sw7 image:
+// lane lm indexes the fragment's 16 output columns (cquad base cq0),
+// regs j = 4 consecutive image rows starting at r0 + (per-lane s>>2).
+DEV bf16x8 abf_tr_rows64(const char* lds_base, int off, int r0, int cq0,
+                         int s4) {
+  s16x4_a v[2];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int row = r0 + half * 4 + (s4 >> 2);
+    const int byte = (off + row * 128 + (cq0 + (s4 & 3)) * 8) ^ ((row & 7) << 4);
+    v[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (abf_las4)(lds_base + byte));
+  }
+  return (bf16x8){v[0][0], v[0][1], v[0][2], v[0][3],
+                  v[1][0], v[1][1], v[1][2], v[1][3]};
+}
+
+// same for the [64 q][128 k] sw15 tiles (256-B rows)
+DEV bf16x8 abf_tr_rows128(const char* lds_base, int off, int r0, int cq0,
+                          int s4) {
+  s16x4_a v[2];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int row = r0 + half * 4 + (s4 >> 2);
+    const int byte = (off + (row & 63) * 256 + (cq0 + (s4 & 3)) * 8) ^
+                     ((row & 15) << 4);
+    v[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (abf_las4)(lds_base + byte));
+  }
+  return (bf16x8){v[0][0], v[0][1], v[0][2], v[0][3],
+                  v[1][0], v[1][1], v[1][2], v[1][3]};
+}
+
+template <int N> DEV void att_zero(f32x4 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// additive mask values for this lane's 8 key columns (col0 + kt*16 + lm);
+// columns past S get -3e38 so they vanish from max and sum.
+DEV void att_mask_cols(float (&mval)[8], bool has_mask,
+                       const ushort_t* __restrict__ mask, int b, int S,
+                       int lm, int col0) {
+#pragma unroll
+  for (int kt = 0; kt < 8; ++kt) {
+    const int col = col0 + kt * 16 + lm;
+    float mv = 0.f;
+    if (has_mask && col < S) mv = bf16_to_f32(mask[(size_t)b * S + col]);
+    mval[kt] = (col < S) ? mv : -3.0e38f;
+  }
+}
+template <bool HAS_MASK>
+DEV void att_mask_cols(float (&mval)[8], const ushort_t* __restrict__ mask,
+                       int b, int S, int lm) {
+  att_mask_cols(mval, HAS_MASK, mask, b, S, lm, 0);
+}
+
+// reductions over the 16 lanes that share one MFMA output row
+DEV float row16_sum(float v) {
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+DEV float row16_max(float v) {
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// score tile: acc[kt] += A B^T for the first nt 16-token tiles of a
+// [tok][64] sw7 LDS image at byte offset off (A = a 16-row fragment pair)
+DEV void att_score_tile(f32x4 (&acc)[8], const bf16x8 (&a)[2], char* lds,
+                        int off, int nt, int lm, int lg) {
+#pragma unroll
+  for (int kt = 0; kt < 8; ++kt) {
+    if (kt >= nt) continue;
+    const int ktok = kt * 16 + lm;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 bk = *(const bf16x8*)lds_at(
+          lds, swz(off + ktok * 128 + (ks * 32 + lg * 8) * 2, ktok, 7));
+      acc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], bk, acc[kt], 0, 0, 0);
+    }
+  }
+}
+
+// stage nrows rows of a [tok][64] bf16 row image (token stride tstride,
+// first token tok0) to LDS offset off via global_load_lds. The XOR swizzle
+// moves to the SOURCE address (lane-linear LDS image == sw7 layout). With
+// clamp, tokens >= S re-read token S-1 (the consumer nulls those rows).
+DEV void att_glds_rows(const ushort_t* src, int tstride, int tok0, int nrows,
+                       bool clamp, int S, char* lds, int off, int tid) {
+  for (int u = tid; u < nrows * 8; u += 256) {
+    const int tok = u >> 3;
+    int gtok = tok0 + tok;
+    if (clamp && gtok >= S) gtok = S - 1;
+    const int c16s = (u & 7) ^ (tok & 7);  // pre-swizzled source column
+    __builtin_amdgcn_global_load_lds(
+        (att_gas)(src + (size_t)gtok * tstride + c16s * 8),
+        (att_las)lds_at(lds, off + u * 16), 16, 0, 0);
+  }
+}
+
+// probability recomputed from the saved row statistics (inv_l = 1 / l)
+DEV float att_prob(float s, float scale, float mv, float m, float inv_l,
+                   bool valid) {
+  float p = __expf(s * scale + mv - m) * inv_l;
+  if (!valid) p = 0.f;
+  return p;
+}
+
+// Dropout of the S <= 128 kernels: lane-local indices, two hashes per
+// (row, lane) cover the lane's 8 key tiles (one 16-bit slice per kt).
+// The forward, probs mode and EVERY backward must draw their keep bits
+// through att_drop_hash + att_drop_keep and nothing else — the mask is
+// regenerated, never stored, so a second definition is a silent bug.
+DEV void att_drop_hash(uint64_t (&z)[2], uint64_t seed, int bh, int S,
+                       int row, int lm) {
+  const uint64_t base = ((uint64_t)bh * S + row) * 16 + lm;
+  z[0] = rng_hash(seed, base * 2);
+  z[1] = rng_hash(seed, base * 2 + 1);
+}
+DEV bool att_drop_keep(const uint64_t (&z)[2], int kt, unsigned keep16) {
+  const uint64_t zz = kt < 4 ? z[0] : z[1];
+  return (unsigned)((zz >> (16 * (kt & 3))) & 0xFFFFu) < keep16;
+}
+
+// store a 16-row x 64-col accumulator tile (MFMA C layout) as bf16 rows
+// row0.. of dst (row stride rstride elements); rows >= S are skipped
+DEV void att_store_rows16(ushort_t* __restrict__ dst, int rstride,
+                          const f32x4 (&acc)[4], int row0, int S, int lm,
+                          int lg) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + lg * 4 + r;
+      if (row < S) dst[(size_t)row * rstride + ct * 16 + lm] = f32_to_bf16(acc[ct][r]);
+    }
+  }
+}
+
+// the same for two tiles on the same rows (dK and dV): each row's two
+// stores issue together, which measures faster than two single calls
+DEV void att_store_rows16x2(ushort_t* __restrict__ d0,
+                            ushort_t* __restrict__ d1, int rstride,
+                            const f32x4 (&a0)[4], const f32x4 (&a1)[4],
+                            int row0, int S, int lm, int lg) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + lg * 4 + r;
+      const int c = ct * 16 + lm;
+      if (row < S) {
+        d0[(size_t)row * rstride + c] = f32_to_bf16(a0[ct][r]);
+        d1[(size_t)row * rstride + c] = f32_to_bf16(a1[ct][r]);
+      }
+    }
+  }
+}
+
+// Launch KERNEL, an expression in the constexpr bool HM such as
+// (attn_bwd1s_kernel<HM>), as its HAS_MASK instantiation picked by the
+// runtime bool has_mask; 256 threads, the argument list written once.
+#define ATT_LAUNCH_HM(has_mask, KERNEL, grid, lds_bytes, stream, ...)         \
+  do {                                                                        \
+    if (has_mask) {                                                           \
+      constexpr bool HM = true;                                               \
+      hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds_bytes, stream,          \
+                         __VA_ARGS__);                                        \
+    } else {                                                                  \
+      constexpr bool HM = false;                                              \
+      hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds_bytes, stream,          \
+                         __VA_ARGS__);                                        \
+    }                                                                         \
+  } while (0)

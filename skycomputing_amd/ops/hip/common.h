@@ -128,6 +128,12 @@ DEV uint64_t rng_hash(uint64_t seed, uint64_t q) {
   return z ^ (z >> 31);
 }
 
+// per-launch seed: the op's salt mixed with the device step counter
+// (null state = counter 0), so masks vary under hipGraph replay
+DEV uint64_t rng_seed(uint64_t salt, const unsigned long long* state) {
+  return salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull;
+}
+
 DEV float rng_uniform(uint64_t seed, uint64_t idx) {
   return (float)(rng_hash(seed, idx) >> 40) * 0x1.0p-24f;
 }

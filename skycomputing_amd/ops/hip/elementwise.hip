@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void dropout_vec_kernel(
     uint64_t salt, const unsigned long long* __restrict__ state) {
   const float inv_keep = 1.f / keep;
   const unsigned keep16 = keep_to_16(keep);
-  const uint64_t seed = salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull;
+  const uint64_t seed = rng_seed(salt, state);
   for (int64_t i8 = (int64_t)blockIdx.x * 256 + threadIdx.x; i8 < n8;
        i8 += (int64_t)gridDim.x * 256) {
     float v[8];
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(
     const void* __restrict__ x, void* __restrict__ y, int64_t n, float keep,
     uint64_t salt, const unsigned long long* __restrict__ state) {
   const float inv_keep = 1.f / keep;
-  const uint64_t seed = salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull;
+  const uint64_t seed = rng_seed(salt, state);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * 256) {
     float v = load_elem<DT>(x, i);

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
   const int wid = threadIdx.x / WAVE;
   const int64_t cols8 = cols / 8;
   const uint64_t seed =
-      DROP ? salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull : 0;
+      DROP ? rng_seed(salt, state) : 0;
   const unsigned keep16 = keep_to_16(keep);
   const float inv_keep = 1.f / keep;
   float v[CH][8];
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_vec_kernel(
   const int wid = threadIdx.x / WAVE;
   const int64_t cols8 = cols / 8;
   const uint64_t seed =
-      DROP ? salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull : 0;
+      DROP ? rng_seed(salt, state) : 0;
   const unsigned keep16 = keep_to_16(keep);
   const float inv_keep = 1.f / keep;
   float xh[CH][8], dxh[CH][8];
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
   const int wid = threadIdx.x / WAVE;
   const int64_t cols8 = cols / 8;
   const uint64_t seed =
-      DROP ? salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull : 0;
+      DROP ? rng_seed(salt, state) : 0;
   const unsigned keep16 = keep_to_16(keep);
   const float inv_keep = 1.f / keep;
   float xh[CH][8], dxh[CH][8];
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_wb_part_kernel(
   const int64_t r0 = slab * rows_per_slab;
   const int64_t r1 = min(rows, r0 + rows_per_slab);
   const uint64_t seed =
-      DROP ? salt + (state ? *state : 0ull) * 0xD1B54A32D192ED03ull : 0;
+      DROP ? rng_seed(salt, state) : 0;
   const unsigned keep16 = keep_to_16(keep);
   const float inv_keep = 1.f / keep;
   float sw[8] = {0.f}, sb[8] = {0.f};

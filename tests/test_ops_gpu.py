@@ -271,6 +271,86 @@ def test_fused_attention_dropout_consistency():
     assert rel < 0.05
 
 
+@pytest.mark.parametrize("S", [128, 48])
+@pytest.mark.parametrize("with_mask", [True, False])
+def test_fused_attention_dropout_mask_shared_by_all_backwards(S, with_mask, monkeypatch):
+    """Forward, probs mode and all three backward paths draw the SAME
+    dropout mask: the keep mask recovered from sky_attn_probs (Pd != 0)
+    feeds an fp32 eager reference, and the forward output and the gradient
+    of every backward path must match it element by element. A path that
+    drew a different mask misses on most elements.
+
+    Tolerances are test_fused_attention_fwd_bwd's (6e-2 out, 8e-2 grad,
+    atol = rtol), kept as they are: the max |err| observed before the
+    kernels shared this code sits well inside them
+    (S, mask: out / split / fused / decomposed grad):
+      128, mask     0.0041 / 0.0098 / 0.0111 / 0.0111
+       48, mask     0.0066 / 0.0119 / 0.0169 / 0.0169
+      128, no mask  0.0045 / 0.0056 / 0.0060 / 0.0060
+       48, no mask  0.0062 / 0.0107 / 0.0110 / 0.0107
+    """
+    from skycomputing_amd.ops.functions import FusedAttentionFn, rng_state
+    from skycomputing_amd.ops.hiplib import check, ptr
+
+    for var in ("SKY_ATTN_FUSED_BWD", "SKY_NO_FUSED_ATTN_BWD"):
+        monkeypatch.delenv(var, raising=False)
+    torch.manual_seed(10)
+    B, h, d = 2, 2, 64
+    scale = 1.0 / d ** 0.5
+    qkv = torch.randn(B, S, 3, h, d, dtype=torch.bfloat16, device="cuda",
+                      requires_grad=True)
+    if with_mask:
+        mask = torch.zeros(B, 1, 1, S, dtype=torch.bfloat16, device="cuda")
+        mask[:, :, :, S - S // 4:] = -10000.0
+    else:
+        mask = None
+    out = FusedAttentionFn.apply(qkv, mask, scale, 0.5, True)
+    dout = torch.randn_like(out)
+
+    fn = out.grad_fn
+    sqkv, smask, m, lsum = fn.saved_tensors
+    P = torch.empty(B, h, S, S, dtype=qkv.dtype, device="cuda")
+    Pd = torch.empty_like(P)
+    check(
+        hiplib.require().sky_attn_probs(
+            torch.cuda.current_stream().cuda_stream, ptr(sqkv), ptr(smask),
+            ptr(m), ptr(lsum), ptr(P), ptr(Pd), B, S, h, d, scale, fn.keep,
+            fn.salt, rng_state().data_ptr(),
+        ),
+        "sky_attn_probs",
+    )
+    keepmask = (Pd != 0).float()
+    assert 0.3 < keepmask.mean().item() < 0.7  # a real keep-0.5 mask
+
+    qf = qkv.detach().float().requires_grad_(True)
+    q = qf[:, :, 0].permute(0, 2, 1, 3)
+    k = qf[:, :, 1].permute(0, 2, 1, 3)
+    v = qf[:, :, 2].permute(0, 2, 1, 3)
+    scores = torch.matmul(q, k.transpose(-1, -2)) * scale
+    if mask is not None:
+        scores = scores + mask.float()
+    probs = torch.softmax(scores, dim=-1) * keepmask / fn.keep
+    ref = torch.matmul(probs, v).permute(0, 2, 1, 3)
+    ref.backward(dout.float())
+
+    err = (out.float() - ref).abs().max().item()
+    print(f"S={S} mask={with_mask} out max|err|={err:.4f}")
+    assert torch.allclose(out.float(), ref, atol=6e-2, rtol=6e-2), err
+
+    for path, env in (("split", None), ("fused", "SKY_ATTN_FUSED_BWD"),
+                      ("decomposed", "SKY_NO_FUSED_ATTN_BWD")):
+        if env is not None:
+            monkeypatch.setenv(env, "1")
+        qkv.grad = None
+        out.backward(dout, retain_graph=True)
+        if env is not None:
+            monkeypatch.delenv(env)
+        err = (qkv.grad.float() - qf.grad).abs().max().item()
+        print(f"S={S} mask={with_mask} {path} grad max|err|={err:.4f}")
+        assert torch.allclose(qkv.grad.float(), qf.grad, atol=8e-2, rtol=8e-2), (
+            path, err)
+
+
 def test_layernorm_fused_dropout_matches_composition():
     """The LN kernel's fused dropout uses the SAME (salt,index) hash scheme
     as the standalone dropout kernel, so with a fixed salt

@@ -127,10 +127,13 @@ class BertSelfOutput(nn.Module):
         self.dropout_p = config.hidden_dropout_prob
 
     def forward(self, hidden, residual):
-        x = self.dense(hidden)
-        # dropout fused into the LN kernel: LN(dropout(x) + residual)
-        return self.layer_norm(x, residual=residual,
-                               dropout_p=self.dropout_p, training=self.training)
+        # one op for dense -> dropout -> residual LN: dropout is fused into
+        # the LN kernel, and on GPU the dense's dbias comes out of the LN
+        # backward pass (ops.linear_residual_layer_norm)
+        return ops.linear_residual_layer_norm(
+            hidden, self.dense.weight, self.dense.bias,
+            self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps,
+            residual, self.dropout_p, self.training)
 
 
 @LAYER.register_module
@@ -252,9 +255,10 @@ class BertLayerTail(nn.Module):
         self.dropout_p = config.hidden_dropout_prob
 
     def forward(self, attn_out, inter, ext_mask):
-        x = self.dense(inter)
-        hidden = self.layer_norm(x, residual=attn_out,
-                                 dropout_p=self.dropout_p, training=self.training)
+        hidden = ops.linear_residual_layer_norm(
+            inter, self.dense.weight, self.dense.bias,
+            self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps,
+            attn_out, self.dropout_p, self.training)
         return hidden, ext_mask
 
     def layer_flops(self, batch: int, seq: int) -> float:

@@ -23,7 +23,8 @@ from .eager import ACT_FNS, gelu, swish  # re-export
 
 __all__ = [
     "layer_norm", "bias_gelu", "bias_tanh", "masked_softmax", "dropout",
-    "attention_context", "linear_act", "embedding_fused", "sgd_step",
+    "attention_context", "linear_act", "linear_residual_layer_norm",
+    "embedding_fused", "sgd_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
 ]
 
@@ -166,6 +167,35 @@ def linear(x, weight, bias=None):
 
         return LinearBiasFn.apply(x, weight, bias)
     return torch.nn.functional.linear(x, weight, bias)
+
+
+def linear_residual_layer_norm(x, weight, bias, ln_weight, ln_bias,
+                               eps: float = 1e-12, residual=None,
+                               dropout_p: float = 0.0, training: bool = False):
+    """LN(dropout(linear(x)) + residual).
+
+    GPU (bias present, fp32/bf16, LayerNorm width supported by the
+    three-sum backward): one autograd node whose backward takes the
+    linear's dbias from the LayerNorm backward pass and runs the weight
+    gradient as a plain GEMM (LinearResidualLayerNormFn). Everything else
+    — CPU, no bias, other widths, SKY_NO_LN_DBIAS=1 — is the composition
+    of ops.linear and ops.layer_norm."""
+    if (
+        bias is not None
+        and x.dtype in (torch.float32, torch.bfloat16)
+        and _use_hip(x)
+    ):
+        from .functions import (
+            LinearResidualLayerNormFn, ln_dbias_enabled, ln_xsum_width_ok,
+        )
+
+        if ln_dbias_enabled() and ln_xsum_width_ok(weight.shape[0]):
+            p = dropout_p if training else 0.0
+            return LinearResidualLayerNormFn.apply(
+                x, weight, bias, ln_weight, ln_bias, eps, residual, p
+            )
+    return layer_norm(linear(x, weight, bias), ln_weight, ln_bias, eps,
+                      residual, dropout_p, training)
 
 
 def linear_act(x, weight, bias, act: str = "gelu"):

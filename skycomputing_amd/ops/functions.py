@@ -701,6 +701,113 @@ class LinearBiasFn(torch.autograd.Function):
         return dx, dw, db
 
 
+def ln_dbias_enabled() -> bool:
+    """SKY_NO_LN_DBIAS=1 keeps linear -> LayerNorm as two Functions (A/B)."""
+    return os.environ.get("SKY_NO_LN_DBIAS") != "1"
+
+
+def ln_xsum_width_ok(cols: int) -> bool:
+    """Row widths the three-sum LayerNorm backward is built for."""
+    return bool(hiplib.require().sky_layernorm_bwd_xsum_ok(cols))
+
+
+class LinearResidualLayerNormFn(torch.autograd.Function):
+    """LN(dropout(x @ W^T + b) + residual) as ONE autograd node, so the
+    backward can take the linear's dbias from the LayerNorm backward pass:
+    d(linear out) is exactly the dx that ln_bwd_dx_cs_kernel holds in
+    registers, and its column sum comes out of the same slab reduction as
+    LN's dw/db (sky_layernorm_bwd_xsum). The weight gradient is then a
+    plain GEMM (sky_hblt_wgrad) instead of the BGRADB-epilogue one plus its
+    post-reduction kernel. Forward kernels, saved tensors and the dropout
+    salt draw are those of LinearBiasFn followed by LayerNormFn."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ln_w, ln_b, eps, residual, dropout_p=0.0):
+        lib = hiplib.require()
+        xs = x.shape
+        x2 = x.reshape(-1, xs[-1])
+        g2 = gemm2_fwd(x2 if x2.is_contiguous() else x2.contiguous(),
+                       weight, bias)
+        if g2 is not None:
+            h = g2[0]
+        else:
+            h = torch.nn.functional.linear(x2, weight, bias)
+        cols = weight.shape[0]
+        h = h.view(*xs[:-1], cols).contiguous()
+        residual = residual.contiguous() if residual is not None else None
+        rows = h.numel() // cols
+        y = torch.empty_like(h)
+        mean = torch.empty(rows, dtype=torch.float32, device=h.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=h.device)
+        keep = 1.0 - dropout_p
+        salt = _next_seed() if keep < 1.0 else 0
+        state_ptr = rng_state().data_ptr() if keep < 1.0 else 0
+        check(
+            lib.sky_layernorm_fwd(
+                _stream(), ptr(h), ptr(residual), ptr(ln_w), ptr(ln_b),
+                ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, _dt(h),
+                keep, salt, state_ptr,
+            ),
+            "sky_layernorm_fwd",
+        )
+        ctx.save_for_backward(x2, weight, h, ln_w, mean, rstd)
+        ctx.residual = residual
+        ctx.has_residual = residual is not None
+        ctx.keep, ctx.salt = keep, salt
+        ctx.xshape = xs
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = hiplib.require()
+        x2, weight, h, ln_w, mean, rstd = ctx.saved_tensors
+        dy = dy.contiguous()
+        cols = h.shape[-1]
+        rows = h.numel() // cols
+        dh = torch.empty_like(h)
+        d_ln_w = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+        d_ln_b = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+        dbias = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+        scratch = _red_scratch(cols, 3, h.device)
+        drop = ctx.keep < 1.0
+        dres = torch.empty_like(h) if (drop and ctx.has_residual) else None
+        state_ptr = rng_state().data_ptr() if drop else 0
+        check(
+            lib.sky_layernorm_bwd_xsum(
+                _stream(), ptr(dy), ptr(h), ptr(ctx.residual), ptr(ln_w),
+                ptr(mean), ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b),
+                ptr(scratch), rows, cols, _dt(h), ctx.keep, ctx.salt,
+                state_ptr, ptr(dres), ptr(dbias),
+            ),
+            "sky_layernorm_bwd_xsum",
+        )
+        if not ctx.has_residual:
+            dgrad_res = None
+        elif drop:
+            dgrad_res = dres
+        else:
+            dgrad_res = dh
+        if dbias.dtype != weight.dtype:
+            dbias = dbias.to(weight.dtype)
+        dh2 = dh.view(-1, cols)
+        dx = gemm2_dgrad(dh2, weight)
+        dx = dx.view(ctx.xshape) if dx is not None else dh2.mm(weight).view(ctx.xshape)
+        xc = x2 if x2.is_contiguous() else x2.contiguous()
+        dw = gemm2_wgrad(dh2, xc)
+        if dw is None and _use_hblt():
+            M, K = xc.shape
+            dw = torch.empty_like(weight)
+            check(
+                lib.sky_hblt_wgrad(
+                    _stream(), ptr(xc), ptr(dh2), ptr(dw), M, cols, K, _dt(xc)
+                ),
+                "sky_hblt_wgrad",
+            )
+        elif dw is None:
+            dw = dh2.t().mm(x2)
+        return dx, dw, dbias, d_ln_w, d_ln_b, None, dgrad_res, None
+
+
 class LinearGeluFn(torch.autograd.Function):
     """Fused linear + bias + GELU via the hipBLASLt GELU_AUX_BIAS epilogue
     (the reference's LinearActivation, scaelum/model/bert_layers.py:60-108):

@@ -1,12 +1,19 @@
 // hipBLASLt epilogue-fused GEMM entry points.
 //
-// Two call sites where a GEMM epilogue absorbs a whole standalone kernel
-// (measured hot spots, profiles/r01_bench160_final_kernels.txt):
+// Call sites where a GEMM epilogue absorbs a whole standalone kernel
+// (measured hot spots, profiles/r01_bench160_final_kernels.txt), plus the
+// plain weight gradient for linears whose dbias comes from elsewhere:
 //
 //  * sky_hblt_wgrad_bgrad — the linear-layer weight gradient
 //    dW[N,K] = dY[M,N]^T @ X[M,K] with the bias gradient
 //    db[n] = sum_m dY[m,n] produced by the BGRADB epilogue, replacing the
 //    separate two-stage column reduction (colsum_part/final) per linear.
+//  * sky_hblt_wgrad — the same weight gradient with the default epilogue,
+//    for a linear whose dbias the following LayerNorm's backward already
+//    produced (ops/hip/layernorm.hip, sky_layernorm_bwd_xsum). Without the
+//    BGRADB epilogue the library is free to pick its fast plain kernels
+//    (BGRADB pins a slower family plus a post-reduction kernel,
+//    profiles/r03_notes.md); selection is measured like the other kinds.
 //  * sky_hblt_linear_gelu_aux — the FFN up-projection
 //    Y = gelu(X @ W^T + b) in one GEMM (GELU_AUX_BIAS), writing the
 //    pre-activation to `aux` for the backward, replacing the separate
@@ -42,7 +49,7 @@ constexpr size_t kMaxWorkspace = 64ull << 20;
 std::mutex g_mu;
 
 struct PlanKey {
-  int kind;  // 0 = wgrad+bgradb, 1 = linear+gelu_aux+bias
+  int kind;  // 0 = wgrad+bgradb, 1 = linear+gelu_aux+bias, 2 = plain wgrad
   int64_t M, N, K;
   int dt;
   int aux_dt;  // DT_* of the saved pre-activation (kind 1 only)
@@ -87,6 +94,7 @@ hipDataType to_hip_dt(int dt) { return dt == DT_BF16 ? HIP_R_16BF : HIP_R_32F; }
 //   kind 0 (wgrad): D(K,N) colmaj [= dW row-major [N,K]] = A(K,M)·op(B),
 //     A = X (colmaj (K,M), op N, lda K), B = dY (colmaj (N,M), op T, ldb N);
 //     the contraction dim is M, so BGRADB sums dY over rows -> db[N].
+//   kind 2 (plain wgrad): kind 0's operands, default epilogue, no bias.
 //   kind 1 (fwd):   D(N,M) colmaj [= Y row-major [M,N]] = op(A)·B,
 //     A = W (colmaj (K,N), op T, lda K), B = X (colmaj (K,M), op N, ldb K);
 //     bias length = D rows = N, broadcast over columns (tokens).
@@ -103,14 +111,16 @@ int get_plan(int kind, int64_t M, int64_t N, int64_t K, int dt, int aux_dt,
   hipDataType hdt = to_hip_dt(dt);
   HBLT_CHECK(hipblasLtMatmulDescCreate(&p.desc, HIPBLAS_COMPUTE_32F, HIP_R_32F));
   int32_t opN = HIPBLAS_OP_N, opT = HIPBLAS_OP_T;
-  if (kind == 0) {
+  if (kind == 0 || kind == 2) {
     HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSA, &opN, sizeof(opN)));
     HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &opT, sizeof(opT)));
-    uint32_t epi = HIPBLASLT_EPILOGUE_BGRADB;
-    HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &epi, sizeof(epi)));
-    int32_t bdt = (int32_t)hdt;
-    HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_DATA_TYPE, &bdt, sizeof(bdt)));
-    HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_or_db, sizeof(bias_or_db)));
+    if (kind == 0) {
+      uint32_t epi = HIPBLASLT_EPILOGUE_BGRADB;
+      HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &epi, sizeof(epi)));
+      int32_t bdt = (int32_t)hdt;
+      HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_DATA_TYPE, &bdt, sizeof(bdt)));
+      HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_or_db, sizeof(bias_or_db)));
+    }
     HBLT_CHECK(hipblasLtMatrixLayoutCreate(&p.la, hdt, K, M, K));   // X
     HBLT_CHECK(hipblasLtMatrixLayoutCreate(&p.lb, hdt, N, M, N));   // dY
     HBLT_CHECK(hipblasLtMatrixLayoutCreate(&p.ld, hdt, K, N, K));   // dW
@@ -207,7 +217,9 @@ int run(int kind, hipStream_t stream, const void* A, const void* B,
   int rc = get_plan(kind, M, N, K, dt, aux_dt, bias_or_db, aux, &p);
   if (rc) return rc;
   // the bias / aux pointers live in the cached desc: refresh per call
-  HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_or_db, sizeof(bias_or_db)));
+  if (kind != 2) {
+    HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_or_db, sizeof(bias_or_db)));
+  }
   if (kind == 1) {
     HBLT_CHECK(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_EPILOGUE_AUX_POINTER, &aux, sizeof(aux)));
   }
@@ -226,6 +238,13 @@ SKY_EXPORT int sky_hblt_wgrad_bgrad(hipStream_t stream, const void* x,
                                     const void* dy, void* dw, void* db,
                                     int64_t M, int64_t N, int64_t K, int dt) {
   return run(0, stream, x, dy, db, nullptr, dw, M, N, K, dt, dt);
+}
+
+// dW[N,K] = dY[M,N]^T @ X[M,K], no epilogue.
+SKY_EXPORT int sky_hblt_wgrad(hipStream_t stream, const void* x,
+                              const void* dy, void* dw, int64_t M, int64_t N,
+                              int64_t K, int dt) {
+  return run(2, stream, x, dy, nullptr, nullptr, dw, M, N, K, dt, dt);
 }
 
 // Y[M,N] = gelu(X[M,K] @ W[N,K]^T + bias[N]); aux[M,N] = pre-activation

@@ -263,7 +263,19 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_vec_kernel(
 // accumulate in registers for free and wb_part's 16-24 MB re-read of
 // dy/x disappears. Each WAVE is one scratch slab (slab = blockIdx*4+wid,
 // no LDS merge); the grid is capped so nslabs <= LN_SLABS.
-template <int DT, bool HAS_RES, bool DROP, int CH>
+//
+// XSUM adds a third column partial: the sum over rows of the value stored
+// to dx (after the dropout mask and 1/keep scaling), accumulated in fp32
+// from the value AS STORED, i.e. rounded to the output dtype first. When
+// the LayerNorm's input is a linear's output, that sum is the linear's
+// bias gradient, and it is then the column sum of exactly the dy that the
+// linear's dgrad and wgrad GEMMs read — what a separate column-sum pass or
+// the BGRADB epilogue computes. (Summing the unrounded fp32 values instead
+// differed from those by the accumulated input rounding, up to 0.05 over
+// 256 rows of unit-scale bf16 gradients.) It costs a few VALU ops per
+// element here and saves the linear a pass over its dy. Slab layout is
+// then [3*cols]: dw, db, dxsum.
+template <int DT, bool HAS_RES, bool DROP, int CH, bool XSUM>
 __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
     const void* __restrict__ dy, const void* __restrict__ x,
     const void* __restrict__ res, const void* __restrict__ w,
@@ -278,12 +290,17 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
       DROP ? rng_seed(salt, state) : 0;
   const unsigned keep16 = keep_to_16(keep);
   const float inv_keep = 1.f / keep;
+  constexpr int NV = XSUM ? 3 : 2;
   float xh[CH][8], dxh[CH][8];
-  float sw[CH][8], sb[CH][8];
+  float sw[CH][8], sb[CH][8], sx[XSUM ? CH : 1][8];
 #pragma unroll
   for (int c = 0; c < CH; ++c)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sw[c][j] = 0.f; sb[c][j] = 0.f; }
+    for (int j = 0; j < 8; ++j) {
+      sw[c][j] = 0.f;
+      sb[c][j] = 0.f;
+      if constexpr (XSUM) sx[c][j] = 0.f;
+    }
   unsigned kbits[CH];
   for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows;
        row += (int64_t)gridDim.x * 4) {
@@ -344,6 +361,11 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
           for (int j = 0; j < 8; ++j)
             o[j] = ((kbits[c] >> j) & 1u) ? o[j] * inv_keep : 0.f;
         }
+        if constexpr (XSUM) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            sx[c][j] += DT == DT_BF16 ? bf16_to_f32(f32_to_bf16(o[j])) : o[j];
+        }
         Vec8<DT>::store(dx, base8 + i8, o);
       }
     }
@@ -351,8 +373,8 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
   // merge the 4 waves' partials through LDS (halves the slab count vs
   // per-wave slabs -> half the scratch the final stage must re-read),
   // then ONE slab write per block.
-  __shared__ float mrg[2][CH * 512];
-  for (int i = threadIdx.x; i < 2 * CH * 512; i += 256)
+  __shared__ float mrg[NV][CH * 512];
+  for (int i = threadIdx.x; i < NV * CH * 512; i += 256)
     (&mrg[0][0])[i] = 0.f;
   __syncthreads();
   for (int k = 0; k < 4; ++k) {
@@ -365,16 +387,18 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
           for (int j = 0; j < 8; ++j) {
             mrg[0][i8 * 8 + j] += sw[c][j];
             mrg[1][i8 * 8 + j] += sb[c][j];
+            if constexpr (XSUM) mrg[NV - 1][i8 * 8 + j] += sx[c][j];
           }
         }
       }
     }
     __syncthreads();
   }
-  float* base = scratch + (int64_t)blockIdx.x * 2 * cols8 * 8;
+  float* base = scratch + (int64_t)blockIdx.x * NV * cols8 * 8;
   for (int i = threadIdx.x; i < cols8 * 8; i += 256) {
     base[i] = mrg[0][i];
     base[cols8 * 8 + i] = mrg[1][i];
+    if constexpr (XSUM) base[2 * cols8 * 8 + i] = mrg[NV - 1][i];
   }
 }
 
@@ -438,66 +462,43 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_wb_part_kernel(
 
 // two-level: a 1024-thread block covers 16 columns x 64 slab-groups,
 // parallel LDS tree, one write per column (see colsum_final_kernel).
-template <int BLOCK, int DTOUT>
+// NV = vectors per slab: 2 (dw, db) or 3 (dw, db, dxsum). (A 4-column,
+// 256-slab-group variant was measured as the 3-vector final at 512 slabs
+// and lost, 23.8 vs 18.6 us for dx_cs + final: profiles/r03_notes.md.)
+template <int BLOCK, int DTOUT, int NV>
 __global__ __launch_bounds__(1024) void ln_bwd_wb_final_kernel(
     const float* __restrict__ scratch, void* __restrict__ dw,
-    void* __restrict__ db, int64_t cols, int64_t nslabs) {
-  __shared__ float ldsw[64][17];
-  __shared__ float ldsb[64][17];
+    void* __restrict__ db, void* __restrict__ dxsum, int64_t cols,
+    int64_t nslabs) {
+  __shared__ float lds[NV][64][17];
   const int c = threadIdx.x & 15;
   const int g = threadIdx.x >> 4;  // 0..63
   const int64_t col = (int64_t)blockIdx.x * 16 + c;
   const int64_t per = (nslabs + 63) / 64;
-  float sw = 0.f, sb = 0.f;
+  float s[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = 0.f;
   if (col < cols) {
     const int64_t y1 = min(nslabs, (int64_t)(g + 1) * per);
     for (int64_t y = (int64_t)g * per; y < y1; ++y) {
-      sw += scratch[y * 2 * cols + col];
-      sb += scratch[y * 2 * cols + cols + col];
+#pragma unroll
+      for (int v = 0; v < NV; ++v) s[v] += scratch[(y * NV + v) * cols + col];
     }
   }
-  ldsw[g][c] = sw;
-  ldsb[g][c] = sb;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) lds[v][g][c] = s[v];
   __syncthreads();
   for (int st = 32; st >= 1; st >>= 1) {
-    if (g < st) { ldsw[g][c] += ldsw[g + st][c]; ldsb[g][c] += ldsb[g + st][c]; }
+    if (g < st) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) lds[v][g][c] += lds[v][g + st][c];
+    }
     __syncthreads();
   }
   if (g == 0 && col < cols) {
-    store_elem<DTOUT>(dw, col, ldsw[0][c]);
-    store_elem<DTOUT>(db, col, ldsb[0][c]);
-  }
-}
-
-// final reduction, CPB=4 columns per 1024-thread block (256 slab-groups):
-// 4x the block count and 4x the per-thread memory-level parallelism of the
-// 16-col variant (that one ran ~1 TB/s on an 8 MB scratch — latency-bound
-// at 64 blocks). Treats scratch as one [nslabs][2*cols] matrix; col >= cols
-// lands in db.
-template <int DTOUT>
-__global__ __launch_bounds__(1024) void ln_bwd_wb_final4_kernel(
-    const float* __restrict__ scratch, void* __restrict__ dw,
-    void* __restrict__ db, int64_t cols, int64_t nslabs) {
-  __shared__ float ldsv[256][5];
-  const int c = threadIdx.x & 3;
-  const int g = threadIdx.x >> 2;  // 0..255
-  const int64_t col = (int64_t)blockIdx.x * 4 + c;
-  const int64_t per = (nslabs + 255) / 256;
-  float s = 0.f;
-  if (col < 2 * cols) {
-    const int64_t y1 = min(nslabs, (int64_t)(g + 1) * per);
-    for (int64_t y = (int64_t)g * per; y < y1; ++y)
-      s += scratch[y * 2 * cols + col];
-  }
-  ldsv[g][c] = s;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (g < st) ldsv[g][c] += ldsv[g + st][c];
-    __syncthreads();
-  }
-  if (g == 0 && col < 2 * cols) {
-    if (col < cols) store_elem<DTOUT>(dw, col, ldsv[0][c]);
-    else store_elem<DTOUT>(db, col - cols, ldsv[0][c]);
+    store_elem<DTOUT>(dw, col, lds[0][0][c]);
+    store_elem<DTOUT>(db, col, lds[1][0][c]);
+    if constexpr (NV == 3) store_elem<DTOUT>(dxsum, col, lds[NV - 1][0][c]);
   }
 }
 
@@ -554,6 +555,68 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_dx_kernel(
   }
 }
 
+// widest chunk count the three-sum (XSUM) dx kernel is built for: CH=2 and
+// CH=4 compile without scratch; CH=8 is at the VGPR limit with two sums
+// already and is not offered.
+#define LN_XSUM_MAXCH 4
+
+// Fused backward: dx (+dres) and the per-block column partials in one
+// kernel, then the final slab reduction. XSUM also produces dxsum[cols],
+// the column sum of the stored dx.
+template <bool XSUM>
+static int ln_bwd_cs_launch(hipStream_t s, uint64_t dy, uint64_t x,
+                            uint64_t res, uint64_t w, uint64_t mean,
+                            uint64_t rstd, uint64_t dx, uint64_t dw,
+                            uint64_t db, uint64_t dxsum, uint64_t scratch,
+                            int64_t rows, int64_t cols, int dt, float keep,
+                            uint64_t salt, uint64_t state, uint64_t dres) {
+  const bool has_res = res != 0;
+  const bool drop = keep < 1.f;
+  // one slab per BLOCK (LDS-merged): grid 512 keeps the dx streaming fed
+  // (256 starved it: 16.9 vs 9.9 us) while the final re-reads only
+  // 512 slabs (SKY_LN_CS_GRID overrides for sweeps)
+  unsigned gmax = 512;
+  if (const char* e = getenv("SKY_LN_CS_GRID")) gmax = (unsigned)atoi(e);
+  if (gmax > LN_SLABS) gmax = LN_SLABS;
+  if (gmax < 1) gmax = 1;
+  unsigned grid = (unsigned)((rows + 3) / 4);
+  if (grid > gmax) grid = gmax;
+  const int ch = (int)((cols / 8 + WAVE - 1) / WAVE);
+#define LNCS(DT, HR, DR, CH)                                                   \
+  hipLaunchKernelGGL((ln_bwd_dx_cs_kernel<DT, HR, DR, CH, XSUM>), dim3(grid),  \
+                     dim3(256), 0, s, (const void*)dy, (const void*)x,         \
+                     (const void*)res, (const void*)w, (const float*)mean,     \
+                     (const float*)rstd, (void*)dx, (void*)dres,               \
+                     (float*)scratch, rows, cols, keep, salt,                  \
+                     (const unsigned long long*)state)
+#define LNCS_CH(DT, HR, DR)                                                    \
+  do {                                                                         \
+    if (ch <= 2) LNCS(DT, HR, DR, 2);                                          \
+    else if (ch <= 4) LNCS(DT, HR, DR, 4);                                     \
+    else if constexpr (!XSUM) LNCS(DT, HR, DR, 8);                             \
+  } while (0)
+#define LNCS_D(DT, HR)                                                         \
+  do { if (drop) LNCS_CH(DT, HR, true); else LNCS_CH(DT, HR, false); } while (0)
+  if (dt == DT_F32) { if (has_res) LNCS_D(DT_F32, true); else LNCS_D(DT_F32, false); }
+  else              { if (has_res) LNCS_D(DT_BF16, true); else LNCS_D(DT_BF16, false); }
+#undef LNCS_D
+#undef LNCS_CH
+#undef LNCS
+  const int64_t nslabs = (int64_t)grid;  // one slab per block
+  constexpr int NV = XSUM ? 3 : 2;
+  dim3 g2((unsigned)((cols + 15) / 16));
+  if (dt == DT_BF16)
+    hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16, NV>), g2,
+                       dim3(1024), 0, s, (const float*)scratch, (void*)dw,
+                       (void*)db, (void*)dxsum, cols, nslabs);
+  else
+    hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32, NV>), g2,
+                       dim3(1024), 0, s, (const float*)scratch, (void*)dw,
+                       (void*)db, (void*)dxsum, cols, nslabs);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
                                  uint64_t res, uint64_t w, uint64_t mean,
                                  uint64_t rstd, uint64_t dx, uint64_t dw,
@@ -570,49 +633,10 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
   // the separate 3-kernel chain for A/B.
   const bool fused_wb =
       ln_fast_ok(cols) && scratch != 0 && !getenv("SKY_LN_SPLIT_WB");
-  if (fused_wb) {
-    // one slab per BLOCK (LDS-merged): grid 512 keeps the dx streaming fed
-    // (256 starved it: 16.9 vs 9.9 us) while the final re-reads only
-    // 512 slabs (SKY_LN_CS_GRID overrides for sweeps)
-    unsigned gmax = 512;
-    if (const char* e = getenv("SKY_LN_CS_GRID")) gmax = (unsigned)atoi(e);
-    if (gmax > LN_SLABS) gmax = LN_SLABS;
-    unsigned grid = (unsigned)((rows + 3) / 4);
-    if (grid > gmax) grid = gmax;
-    const int ch = (int)((cols / 8 + WAVE - 1) / WAVE);
-#define LNCS(DT, HR, DR, CH)                                                   \
-  hipLaunchKernelGGL((ln_bwd_dx_cs_kernel<DT, HR, DR, CH>), dim3(grid),        \
-                     dim3(256), 0, s, (const void*)dy, (const void*)x,         \
-                     (const void*)res, (const void*)w, (const float*)mean,     \
-                     (const float*)rstd, (void*)dx, (void*)dres,               \
-                     (float*)scratch, rows, cols, keep, salt,                  \
-                     (const unsigned long long*)state)
-#define LNCS_CH(DT, HR, DR)                                                    \
-  do {                                                                         \
-    if (ch <= 2) LNCS(DT, HR, DR, 2);                                          \
-    else if (ch <= 4) LNCS(DT, HR, DR, 4);                                     \
-    else LNCS(DT, HR, DR, 8);                                                  \
-  } while (0)
-#define LNCS_D(DT, HR)                                                         \
-  do { if (drop) LNCS_CH(DT, HR, true); else LNCS_CH(DT, HR, false); } while (0)
-    if (dt == DT_F32) { if (has_res) LNCS_D(DT_F32, true); else LNCS_D(DT_F32, false); }
-    else              { if (has_res) LNCS_D(DT_BF16, true); else LNCS_D(DT_BF16, false); }
-#undef LNCS_D
-#undef LNCS_CH
-#undef LNCS
-    const int64_t nslabs = (int64_t)grid;  // one slab per block
-    dim3 g2((unsigned)((cols + 15) / 16));
-    if (dt == DT_BF16)
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16>), g2, dim3(1024),
-                         0, s, (const float*)scratch, (void*)dw, (void*)db,
-                         cols, nslabs);
-    else
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32>), g2, dim3(1024),
-                         0, s, (const float*)scratch, (void*)dw, (void*)db,
-                         cols, nslabs);
-    LAUNCH_CHECK();
-    return 0;
-  }
+  if (fused_wb)
+    return ln_bwd_cs_launch<false>(s, dy, x, res, w, mean, rstd, dx, dw, db, 0,
+                                   scratch, rows, cols, dt, keep, salt, state,
+                                   dres);
   if (ln_fast_ok(cols)) {
     unsigned grid = (unsigned)((rows + 3) / 4);
     if (grid > 8192u) grid = 8192u;
@@ -673,13 +697,13 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
 #undef LNWBP
     dim3 g2((unsigned)((cols + 15) / 16));
     if (dt == DT_BF16)
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16>), g2, dim3(1024),
-                         0, s, (const float*)scratch, (void*)dw, (void*)db,
-                         cols, nslabs);
+      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16, 2>), g2,
+                         dim3(1024), 0, s, (const float*)scratch, (void*)dw,
+                         (void*)db, (void*)nullptr, cols, nslabs);
     else
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32>), g2, dim3(1024),
-                         0, s, (const float*)scratch, (void*)dw, (void*)db,
-                         cols, nslabs);
+      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32, 2>), g2,
+                         dim3(1024), 0, s, (const float*)scratch, (void*)dw,
+                         (void*)db, (void*)nullptr, cols, nslabs);
   } else {
     constexpr int BLOCK = 256;
     // slab sized so the grid fills 256 CUs (cols/256 col-blocks * row-slabs)
@@ -699,4 +723,28 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
   }
   LAUNCH_CHECK();
   return 0;
+}
+
+// 1 if sky_layernorm_bwd_xsum supports this row width.
+SKY_EXPORT int sky_layernorm_bwd_xsum_ok(int64_t cols) {
+  return cols > 0 && cols % 8 == 0 && cols <= 64 * 8 * LN_XSUM_MAXCH;
+}
+
+// sky_layernorm_bwd plus dxsum[cols] = column sum of the stored dx (param
+// dtype, like dw/db): the bias gradient of a linear feeding this LayerNorm.
+// Always the fused dx + column-partials path; needs scratch of
+// [LN_SLABS][3*cols] fp32. Unsupported widths return an error so the
+// caller composes the two ops instead.
+SKY_EXPORT int sky_layernorm_bwd_xsum(uint64_t stream, uint64_t dy, uint64_t x,
+                                      uint64_t res, uint64_t w, uint64_t mean,
+                                      uint64_t rstd, uint64_t dx, uint64_t dw,
+                                      uint64_t db, uint64_t scratch,
+                                      int64_t rows, int64_t cols, int dt,
+                                      float keep, uint64_t salt, uint64_t state,
+                                      uint64_t dres, uint64_t dxsum) {
+  if (!sky_layernorm_bwd_xsum_ok(cols) || scratch == 0 || dxsum == 0)
+    return (int)hipErrorInvalidValue;
+  return ln_bwd_cs_launch<true>((hipStream_t)stream, dy, x, res, w, mean, rstd,
+                                dx, dw, db, dxsum, scratch, rows, cols, dt,
+                                keep, salt, state, dres);
 }

@@ -35,6 +35,9 @@ def _register_signatures(lib):
         #        strm x res w b y mean rstd rows cols eps dt keep salt state
         "sky_layernorm_bwd": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64],
         #        strm dy x res w mean rstd dx dw db scratch | rows cols dt keep salt state dres
+        "sky_layernorm_bwd_xsum": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64],
+        #        sky_layernorm_bwd's arguments + dxsum (column sum of the stored dx)
+        "sky_layernorm_bwd_xsum_ok": [i64],  # cols -> 1 if the width is supported
         "sky_bias_gelu_fwd": [u64, u64, u64, u64, i64, i64, i32],
         #                     strm  x    b    y    rows cols dt
         "sky_bias_gelu_bwd": [u64, u64, u64, u64, u64, u64, u64, i64, i64, i32],
@@ -56,6 +59,7 @@ def _register_signatures(lib):
         "sky_rng_tick": [u64, u64],  # strm, state ptr
         "sky_colsum": [u64, u64, u64, u64, i64, i64, i32, i32],  # strm src out scratch rows cols dt dtout
         "sky_hblt_wgrad_bgrad": [u64, u64, u64, u64, u64, i64, i64, i64, i32],  # strm x dy dw db M N K dt
+        "sky_hblt_wgrad": [u64, u64, u64, u64, i64, i64, i64, i32],  # strm x dy dw M N K dt
         "sky_hblt_linear_gelu_aux": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i32, i32],  # strm x w bias y aux M N K dt aux_dt
         "sky_mfma_probe": [u64, u64, u64, u64],  # strm A B D
         "sky_glds_probe": [u64, u64, u64, i32],

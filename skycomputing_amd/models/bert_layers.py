@@ -195,9 +195,16 @@ class BertLayerHead(nn.Module):
         self.output = BertSelfOutput(config)
 
     def forward(self, hidden, ext_mask):
-        attn = self.attention(hidden, ext_mask)
-        out = self.output(attn, hidden)
-        return out, ext_mask
+        # one op for qkv -> attention -> dense -> dropout -> residual LN
+        # (what self.output(self.attention(hidden, ext_mask), hidden)
+        # computes): on GPU a single autograd node, see ops.attention_block
+        att, out = self.attention, self.output
+        y = ops.attention_block(
+            hidden, ext_mask, att.qkv.weight, att.qkv.bias, att.num_heads,
+            att.dropout_p, out.dense.weight, out.dense.bias,
+            out.layer_norm.weight, out.layer_norm.bias, out.layer_norm.eps,
+            out.dropout_p, self.training)
+        return y, ext_mask
 
     def layer_flops(self, batch: int, seq: int) -> float:
         H = self.config.hidden_size

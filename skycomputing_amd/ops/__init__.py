@@ -23,7 +23,8 @@ from .eager import ACT_FNS, gelu, swish  # re-export
 
 __all__ = [
     "layer_norm", "bias_gelu", "bias_tanh", "masked_softmax", "dropout",
-    "attention_context", "linear_act", "linear_residual_layer_norm",
+    "attention_context", "attention_block", "linear_act",
+    "linear_residual_layer_norm",
     "embedding_fused", "sgd_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
 ]
@@ -196,6 +197,51 @@ def linear_residual_layer_norm(x, weight, bias, ln_weight, ln_bias,
             )
     return layer_norm(linear(x, weight, bias), ln_weight, ln_bias, eps,
                       residual, dropout_p, training)
+
+
+def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
+                    attn_dropout_p: float, out_weight, out_bias, ln_weight,
+                    ln_bias, eps: float = 1e-12, hidden_dropout_p: float = 0.0,
+                    training: bool = False):
+    """The attention third of an encoder block:
+    LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
+    for hidden [B, S, H], mask [B, 1, 1, S] additive or None.
+
+    GPU, bf16, head dim 64, S <= 128, both biases present and the
+    LayerNorm width supported by the three-sum backward: one autograd node
+    (AttentionBlockFn) whose backward takes the qkv dbias from the
+    attention backward kernels and sums hidden's two gradients inside the
+    qkv dgrad GEMM. Everything else — CPU, fp32, long sequences,
+    SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
+    paths — is the composition of ops.linear, ops.attention and
+    ops.linear_residual_layer_norm."""
+    B, S, H = hidden.shape
+    d = H // num_heads
+    if (
+        hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
+        and S <= 128 and qkv_bias is not None and out_bias is not None
+        and hiplib.available()
+        and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
+        and os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1"
+        and os.environ.get("SKY_ATTN_FUSED_BWD") != "1"
+    ):
+        from .functions import (
+            AttentionBlockFn, attn_block_enabled, ln_dbias_enabled,
+            ln_xsum_width_ok,
+        )
+
+        if attn_block_enabled() and ln_dbias_enabled() and ln_xsum_width_ok(H):
+            ap = attn_dropout_p if (training and attn_dropout_p > 0) else 0.0
+            hp = hidden_dropout_p if training else 0.0
+            return AttentionBlockFn.apply(
+                hidden, qkv_weight, qkv_bias, mask, num_heads, ap,
+                out_weight, out_bias, ln_weight, ln_bias, eps, hp
+            )
+    qkv = linear(hidden, qkv_weight, qkv_bias).view(B, S, 3, num_heads, d)
+    attn = attention(qkv, mask, attn_dropout_p, training)
+    return linear_residual_layer_norm(
+        attn, out_weight, out_bias, ln_weight, ln_bias, eps, hidden,
+        hidden_dropout_p, training)
 
 
 def linear_act(x, weight, bias, act: str = "gelu"):

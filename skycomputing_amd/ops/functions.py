@@ -8,6 +8,7 @@ fp32 (tests/test_ops_gpu.py).
 
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -301,6 +302,38 @@ def _attn_bwd_decomposed(qkv, P, Pd, dout, scale, dP_of):
     return dqkv
 
 
+def _attn_fwd(qkv, mask, scale, keep):
+    """sky_attn_fwd on a contiguous packed qkv [B, S, 3, h, 64]; draws the
+    dropout salt when keep < 1. Returns (out [B, S, h, d], m, lsum, salt)."""
+    lib = hiplib.require()
+    B, S, _, h, d = qkv.shape
+    out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
+    m = torch.empty(B, h, S, dtype=torch.float32, device=qkv.device)
+    lsum = torch.empty_like(m)
+    salt = _next_seed() if keep < 1.0 else 0
+    state = rng_state()
+    check(
+        lib.sky_attn_fwd(
+            _stream(), ptr(qkv), ptr(mask), ptr(out), ptr(m), ptr(lsum),
+            B, S, h, d, scale, keep, salt, state.data_ptr(),
+        ),
+        "sky_attn_fwd",
+    )
+    return out, m, lsum, salt
+
+
+def _attn_bwd_scratch(qkv):
+    """The two-kernel backward's transposed scratch (pdT, dsT), [B,h,S,S]
+    each. bwd2 loads whole 32-q fragments, so for S % 32 != 0 the last
+    row's load runs past the tensor; zero B rows null it only if those
+    bytes are finite -> zeroed tail."""
+    B, S, _, h, _ = qkv.shape
+    alloc = torch.empty if S == 128 else torch.zeros
+    n = B * h * S * S + (32 if S % 32 else 0)
+    return (alloc(n, dtype=qkv.dtype, device=qkv.device),
+            alloc(n, dtype=qkv.dtype, device=qkv.device))
+
+
 class FusedAttentionFn(torch.autograd.Function):
     """Fused attention: out = dropout(softmax(scale*QK^T + mask)) V in ONE
     MFMA kernel (ops/hip/attention.hip); S x S probabilities are never
@@ -318,24 +351,12 @@ class FusedAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, mask, scale, dropout_p, training):
-        lib = hiplib.require()
         B, S, three, h, d = qkv.shape
         assert three == 3 and d == 64 and S <= 128
         qkv = qkv.contiguous()
         mask = mask.contiguous() if mask is not None else None
-        out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
-        m = torch.empty(B, h, S, dtype=torch.float32, device=qkv.device)
-        lsum = torch.empty_like(m)
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
-        salt = _next_seed() if keep < 1.0 else 0
-        state = rng_state()
-        check(
-            lib.sky_attn_fwd(
-                _stream(), ptr(qkv), ptr(mask), ptr(out), ptr(m), ptr(lsum),
-                B, S, h, d, scale, keep, salt, state.data_ptr(),
-            ),
-            "sky_attn_fwd",
-        )
+        out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep)
         ctx.save_for_backward(qkv, mask, m, lsum)
         ctx.scale, ctx.keep, ctx.salt = scale, keep, salt
         return out
@@ -364,13 +385,7 @@ class FusedAttentionFn(torch.autograd.Function):
                 )
                 return dqkv, None, None, None, None
             # two-kernel path (bwd1s + bwd2 over transposed scratch)
-            # scratch [B,h,S,S]. bwd2 loads whole 32-q fragments, so for
-            # S % 32 != 0 the last row's load runs past the tensor; zero
-            # B rows null it only if those bytes are finite -> zeroed tail
-            alloc = torch.empty if S == 128 else torch.zeros
-            n = B * h * S * S + (32 if S % 32 else 0)
-            pdT = alloc(n, dtype=qkv.dtype, device=dev)
-            dsT = alloc(n, dtype=qkv.dtype, device=dev)
+            pdT, dsT = _attn_bwd_scratch(qkv)
             check(
                 lib.sky_attn_bwd(
                     _stream(), ptr(qkv), ptr(dout), ptr(mask), ptr(m),
@@ -649,6 +664,42 @@ def gemm2_wgrad(dy2, x2):
     return dw
 
 
+def _linear_fwd(x2, weight, bias):
+    """y = x2 @ weight.T + bias on 2D x2: the v2 hand GEMM where the site is
+    enabled for the shape, torch (hipBLASLt) otherwise."""
+    g2 = gemm2_fwd(x2 if x2.is_contiguous() else x2.contiguous(), weight, bias)
+    if g2 is not None:
+        return g2[0]
+    return torch.nn.functional.linear(x2, weight, bias)
+
+
+def _wgrad_plain(dy2, x2, weight):
+    """dW = dy2.T @ x2 for a linear whose dbias comes from elsewhere: the
+    v2 hand GEMM if enabled, else a plain hipBLASLt GEMM with measured
+    algorithm selection (sky_hblt_wgrad), else torch (SKY_NO_HBLT=1)."""
+    xc = x2 if x2.is_contiguous() else x2.contiguous()
+    dw = gemm2_wgrad(dy2, xc)
+    if dw is None and _use_hblt():
+        M, K = xc.shape
+        dw = torch.empty_like(weight)
+        check(
+            hiplib.require().sky_hblt_wgrad(
+                _stream(), ptr(xc), ptr(dy2), ptr(dw), M, weight.shape[0], K,
+                _dt(xc)
+            ),
+            "sky_hblt_wgrad",
+        )
+    elif dw is None:
+        dw = dy2.t().mm(x2)
+    return dw
+
+
+def _dgrad(dy2, weight):
+    """dx = dy2 @ weight (2D)."""
+    dx = gemm2_dgrad(dy2, weight)
+    return dx if dx is not None else dy2.mm(weight)
+
+
 class LinearBiasFn(torch.autograd.Function):
     """Linear + bias with a custom backward: dgrad stays a hipBLASLt GEMM;
     wgrad is a direct hipBLASLt call whose BGRADB epilogue produces dbias
@@ -660,12 +711,7 @@ class LinearBiasFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        g2 = gemm2_fwd(x2 if x2.is_contiguous() else x2.contiguous(),
-                       weight, bias)
-        if g2 is not None:
-            y = g2[0]
-        else:
-            y = torch.nn.functional.linear(x2, weight, bias)
+        y = _linear_fwd(x2, weight, bias)
         ctx.save_for_backward(x2, weight)
         ctx.xshape = xs
         ctx.has_bias = bias is not None
@@ -711,6 +757,55 @@ def ln_xsum_width_ok(cols: int) -> bool:
     return bool(hiplib.require().sky_layernorm_bwd_xsum_ok(cols))
 
 
+def _ln_fwd(h, residual, ln_w, ln_b, eps, keep):
+    """sky_layernorm_fwd: LN(dropout(h) + residual) on contiguous inputs;
+    draws the dropout salt when keep < 1. Returns (y, mean, rstd, salt)."""
+    cols = h.shape[-1]
+    rows = h.numel() // cols
+    y = torch.empty_like(h)
+    mean = torch.empty(rows, dtype=torch.float32, device=h.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=h.device)
+    salt = _next_seed() if keep < 1.0 else 0
+    state_ptr = rng_state().data_ptr() if keep < 1.0 else 0
+    check(
+        hiplib.require().sky_layernorm_fwd(
+            _stream(), ptr(h), ptr(residual), ptr(ln_w), ptr(ln_b),
+            ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, _dt(h),
+            keep, salt, state_ptr,
+        ),
+        "sky_layernorm_fwd",
+    )
+    return y, mean, rstd, salt
+
+
+def _ln_bwd_xsum(dy, h, residual, ln_w, mean, rstd, keep, salt):
+    """sky_layernorm_bwd_xsum: returns (dh, d_ln_w, d_ln_b, dxsum, dres)
+    with dxsum the column sum of dh as stored and dres the residual's
+    gradient (dh itself without dropout, None without a residual)."""
+    cols = h.shape[-1]
+    rows = h.numel() // cols
+    dh = torch.empty_like(h)
+    d_ln_w = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+    d_ln_b = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+    dxsum = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
+    scratch = _red_scratch(cols, 3, h.device)
+    drop = keep < 1.0
+    dres = torch.empty_like(h) if (drop and residual is not None) else None
+    state_ptr = rng_state().data_ptr() if drop else 0
+    check(
+        hiplib.require().sky_layernorm_bwd_xsum(
+            _stream(), ptr(dy), ptr(h), ptr(residual), ptr(ln_w),
+            ptr(mean), ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b),
+            ptr(scratch), rows, cols, _dt(h), keep, salt,
+            state_ptr, ptr(dres), ptr(dxsum),
+        ),
+        "sky_layernorm_bwd_xsum",
+    )
+    if residual is not None and not drop:
+        dres = dh
+    return dh, d_ln_w, d_ln_b, dxsum, dres
+
+
 class LinearResidualLayerNormFn(torch.autograd.Function):
     """LN(dropout(x @ W^T + b) + residual) as ONE autograd node, so the
     backward can take the linear's dbias from the LayerNorm backward pass:
@@ -723,33 +818,13 @@ class LinearResidualLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, ln_w, ln_b, eps, residual, dropout_p=0.0):
-        lib = hiplib.require()
         xs = x.shape
         x2 = x.reshape(-1, xs[-1])
-        g2 = gemm2_fwd(x2 if x2.is_contiguous() else x2.contiguous(),
-                       weight, bias)
-        if g2 is not None:
-            h = g2[0]
-        else:
-            h = torch.nn.functional.linear(x2, weight, bias)
         cols = weight.shape[0]
-        h = h.view(*xs[:-1], cols).contiguous()
+        h = _linear_fwd(x2, weight, bias).view(*xs[:-1], cols).contiguous()
         residual = residual.contiguous() if residual is not None else None
-        rows = h.numel() // cols
-        y = torch.empty_like(h)
-        mean = torch.empty(rows, dtype=torch.float32, device=h.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=h.device)
         keep = 1.0 - dropout_p
-        salt = _next_seed() if keep < 1.0 else 0
-        state_ptr = rng_state().data_ptr() if keep < 1.0 else 0
-        check(
-            lib.sky_layernorm_fwd(
-                _stream(), ptr(h), ptr(residual), ptr(ln_w), ptr(ln_b),
-                ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, _dt(h),
-                keep, salt, state_ptr,
-            ),
-            "sky_layernorm_fwd",
-        )
+        y, mean, rstd, salt = _ln_fwd(h, residual, ln_w, ln_b, eps, keep)
         ctx.save_for_backward(x2, weight, h, ln_w, mean, rstd)
         ctx.residual = residual
         ctx.has_residual = residual is not None
@@ -759,53 +834,108 @@ class LinearResidualLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = hiplib.require()
         x2, weight, h, ln_w, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        cols = h.shape[-1]
-        rows = h.numel() // cols
-        dh = torch.empty_like(h)
-        d_ln_w = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-        d_ln_b = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-        dbias = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-        scratch = _red_scratch(cols, 3, h.device)
-        drop = ctx.keep < 1.0
-        dres = torch.empty_like(h) if (drop and ctx.has_residual) else None
-        state_ptr = rng_state().data_ptr() if drop else 0
-        check(
-            lib.sky_layernorm_bwd_xsum(
-                _stream(), ptr(dy), ptr(h), ptr(ctx.residual), ptr(ln_w),
-                ptr(mean), ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b),
-                ptr(scratch), rows, cols, _dt(h), ctx.keep, ctx.salt,
-                state_ptr, ptr(dres), ptr(dbias),
-            ),
-            "sky_layernorm_bwd_xsum",
-        )
-        if not ctx.has_residual:
-            dgrad_res = None
-        elif drop:
-            dgrad_res = dres
-        else:
-            dgrad_res = dh
+        dh, d_ln_w, d_ln_b, dbias, dgrad_res = _ln_bwd_xsum(
+            dy.contiguous(), h, ctx.residual, ln_w, mean, rstd, ctx.keep,
+            ctx.salt)
         if dbias.dtype != weight.dtype:
             dbias = dbias.to(weight.dtype)
-        dh2 = dh.view(-1, cols)
-        dx = gemm2_dgrad(dh2, weight)
-        dx = dx.view(ctx.xshape) if dx is not None else dh2.mm(weight).view(ctx.xshape)
-        xc = x2 if x2.is_contiguous() else x2.contiguous()
-        dw = gemm2_wgrad(dh2, xc)
-        if dw is None and _use_hblt():
-            M, K = xc.shape
-            dw = torch.empty_like(weight)
-            check(
-                lib.sky_hblt_wgrad(
-                    _stream(), ptr(xc), ptr(dh2), ptr(dw), M, cols, K, _dt(xc)
-                ),
-                "sky_hblt_wgrad",
-            )
-        elif dw is None:
-            dw = dh2.t().mm(x2)
+        dh2 = dh.view(-1, h.shape[-1])
+        dx = _dgrad(dh2, weight).view(ctx.xshape)
+        dw = _wgrad_plain(dh2, x2, weight)
         return dx, dw, dbias, d_ln_w, d_ln_b, None, dgrad_res, None
+
+
+def attn_block_enabled() -> bool:
+    """SKY_NO_ATTN_BLOCK=1 keeps the attention third of an encoder block as
+    its three autograd nodes (A/B)."""
+    return os.environ.get("SKY_NO_ATTN_BLOCK") != "1"
+
+
+class AttentionBlockFn(torch.autograd.Function):
+    """The attention third of an encoder block as ONE autograd node:
+
+        LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
+
+    Forward kernels, saved tensors and the order of the two dropout-salt
+    draws are those of LinearBiasFn, FusedAttentionFn and
+    LinearResidualLayerNormFn in sequence, so y is bit-identical to that
+    composition. One node lets the backward
+      * take the qkv linear's dbias from the attention backward kernels,
+        which hold dQ / dK / dV in registers (sky_attn_bwd_dbias), so the
+        qkv weight gradient is a plain GEMM instead of the BGRADB-epilogue
+        one plus its post-reduction kernel, and
+      * fold autograd's add of hidden's two gradients (residual branch and
+        qkv linear) into the qkv dgrad GEMM (beta = 1 on dres).
+    bf16, d = 64, S <= 128 only (the fused attention kernels' domain);
+    mask [B, 1, 1, S] additive or None."""
+
+    @staticmethod
+    def forward(ctx, hidden, wqkv, bqkv, mask, num_heads, attn_p, wo, bo,
+                ln_w, ln_b, eps, hidden_p):
+        B, S, H = hidden.shape
+        d = H // num_heads
+        assert d == 64 and S <= 128 and hidden.dtype == torch.bfloat16
+        hidden = hidden.contiguous()
+        x2 = hidden.view(-1, H)
+        qkv = _linear_fwd(x2, wqkv, bqkv).view(B, S, 3, num_heads, d)
+        mask = mask.contiguous() if mask is not None else None
+        scale = 1.0 / math.sqrt(d)
+        akeep = 1.0 - attn_p
+        ctxl, m, lsum, asalt = _attn_fwd(qkv, mask, scale, akeep)
+        c2 = ctxl.view(-1, H)
+        h = _linear_fwd(c2, wo, bo).view(B, S, H)
+        keep = 1.0 - hidden_p
+        y, mean, rstd, salt = _ln_fwd(h, hidden, ln_w, ln_b, eps, keep)
+        ctx.save_for_backward(x2, wqkv, qkv, mask, m, lsum, c2, wo, h, ln_w,
+                              mean, rstd)
+        ctx.scale, ctx.akeep, ctx.asalt = scale, akeep, asalt
+        ctx.keep, ctx.salt = keep, salt
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = hiplib.require()
+        (x2, wqkv, qkv, mask, m, lsum, c2, wo, h, ln_w, mean,
+         rstd) = ctx.saved_tensors
+        B, S, _, nh, d = qkv.shape
+        H = nh * d
+        dh, d_ln_w, d_ln_b, dbo, dres = _ln_bwd_xsum(
+            dy.contiguous(), h, x2, ln_w, mean, rstd, ctx.keep, ctx.salt)
+        dh2 = dh.view(-1, H)
+        dctx = _dgrad(dh2, wo)
+        dwo = _wgrad_plain(dh2, c2, wo)
+        dqkv = torch.empty_like(qkv)
+        dbqkv = torch.empty(3 * H, dtype=wqkv.dtype, device=qkv.device)
+        pdT, dsT = _attn_bwd_scratch(qkv)
+        # column partials of dqkv, one slab per (batch, 64-query block);
+        # the kernels write every element, so no memset
+        slabs = torch.empty(B * ((S + 63) // 64) * 3 * H, dtype=torch.float32,
+                            device=qkv.device)
+        check(
+            lib.sky_attn_bwd_dbias(
+                _stream(), ptr(qkv), ptr(dctx), ptr(mask), ptr(m), ptr(lsum),
+                ptr(pdT), ptr(dsT), ptr(dqkv), B, S, nh, d, ctx.scale,
+                ctx.akeep, ctx.asalt, rng_state().data_ptr(), ptr(slabs),
+                ptr(dbqkv), _dt(dbqkv),
+            ),
+            "sky_attn_bwd_dbias",
+        )
+        dqkv2 = dqkv.view(-1, 3 * H)
+        dwqkv = _wgrad_plain(dqkv2, x2, wqkv)
+        # d hidden = dres + dqkv @ Wqkv, accumulated by the GEMM. Without
+        # dropout dres IS dh; its readers above are already enqueued on
+        # this stream, so updating it in place is safe.
+        dres2 = dres.view(-1, H)
+        g2 = gemm2_dgrad(dqkv2, wqkv)
+        if g2 is not None:
+            dres2.add_(g2)
+        else:
+            dres2.addmm_(dqkv2, wqkv)
+        if dbo.dtype != wo.dtype:
+            dbo = dbo.to(wo.dtype)
+        return (dres.view(B, S, H), dwqkv, dbqkv, None, None, None, dwo, dbo,
+                d_ln_w, d_ln_b, None, None)
 
 
 class LinearGeluFn(torch.autograd.Function):

@@ -24,16 +24,23 @@
 // and 2 waves/SIMD, latency-bound; with a 16-row per-wave dS buffer the
 // block fits 48 KB LDS -> 3 blocks/CU at 3+ waves/SIMD and 2x the
 // workgroups (bwd pair 60.8 -> 49.2 us, profiles/r01_notes.md).
-template <bool HAS_MASK>
+//
+// DBIAS (sky_attn_bwd_dbias): the block also writes the column sums of its
+// stored dQ tile, 64 floats, to columns hh*64.. of slab b*QB + qb of the
+// fp32 scratch dbscr [B*QB][3*h*64]; with attn_bwd2_kernel's dK/dV sums
+// every (slab, column) is written exactly once, so the scratch needs no
+// memset and the slab reduction (colsum_final) is deterministic.
+template <bool HAS_MASK, bool DBIAS>
 __global__ __launch_bounds__(256, 3) void attn_bwd1s_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
     const float* __restrict__ l_io, ushort_t* __restrict__ pdT,
     ushort_t* __restrict__ dsT, ushort_t* __restrict__ dqkv, int B, int S,
     int h, float scale, float keep, uint64_t salt,
-    const unsigned long long* __restrict__ state) {
+    const unsigned long long* __restrict__ state, float* __restrict__ dbscr) {
   // LDS: V [128][64] sw7 @0 (16K), K [128][64] sw7 @16K, per-wave dS
-  // [16][128] sw15 @32K + w*4K. Total 48K.
+  // [16][128] sw15 @32K + w*4K. Total 48K. DBIAS reuses the first 1 KB of
+  // the V image, dead once phase A is over, for the per-wave column sums.
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int l = tid & 63;
@@ -169,6 +176,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd1s_kernel(
   }
   __syncthreads();  // dS tiles complete before the dQ MFMAs read them
 
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
   if (active) {
     // dQ = dS K : A = this wave's dS rows (LDS), B = K^T via tr16
     f32x4 qacc[4];
@@ -186,14 +194,36 @@ __global__ __launch_bounds__(256, 3) void attn_bwd1s_kernel(
     }
     ushort_t* dq = dqkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
     att_store_rows16(dq, ts, qacc, qtok_base, S, lm, lg);
+    if constexpr (DBIAS) att_colsum_rows16(cs, qacc, qtok_base, S, lg);
+  }
+  if constexpr (DBIAS) {
+    // every wave has passed the barrier above, so nobody reads V any more;
+    // inactive waves contribute their zeros and must reach the barrier too
+    float* wsum = (float*)lds_at(lds, 0);  // [4 waves][64 cols]
+    att_colsum_wave(cs);
+    if (lg == 0) {
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) wsum[w * 64 + ct * 16 + lm] = cs[ct];
+    }
+    __syncthreads();
+    if (tid < 64)
+      dbscr[((size_t)b * QB + qb) * ts + (size_t)hh * ATT_D + tid] =
+          (wsum[tid] + wsum[64 + tid]) + (wsum[128 + tid] + wsum[192 + tid]);
   }
 }
 
+// DBIAS: the block writes the column sums of its stored dK and dV tiles to
+// slab b*QB of dbscr (see attn_bwd1s_kernel) and zeros to the same columns
+// of the batch's other QB-1 slabs. Launched with 2 KB more LDS for the
+// per-wave sums [4 waves][dK 64 | dV 64] @32K.
+template <bool DBIAS>
 __global__ __launch_bounds__(256) void attn_bwd2_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ pdT, const ushort_t* __restrict__ dsT,
-    ushort_t* __restrict__ dqkv, int B, int S, int h) {
-  // LDS: Qt [64][128] sw15 @0 (16K), dOt [64][128] sw15 @16K. Total 32K.
+    ushort_t* __restrict__ dqkv, int B, int S, int h,
+    float* __restrict__ dbscr) {
+  // LDS: Qt [64][128] sw15 @0 (16K), dOt [64][128] sw15 @16K. Total 32K
+  // (+ 2K of column sums @32K with DBIAS).
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int l = tid & 63;
@@ -226,6 +256,7 @@ __global__ __launch_bounds__(256) void attn_bwd2_kernel(
   __syncthreads();
 
   const int kt0 = 2 * w;  // this wave's two 16-row k tiles
+  float ck[4] = {0.f, 0.f, 0.f, 0.f}, cv[4] = {0.f, 0.f, 0.f, 0.f};
   for (int ki = 0; ki < 2; ++ki) {
     const int ktok_base = (kt0 + ki) * 16;
     if (ktok_base >= S) break;
@@ -252,6 +283,31 @@ __global__ __launch_bounds__(256) void attn_bwd2_kernel(
     ushort_t* dk = dqkv + (size_t)b * S * ts + (size_t)(h + hh) * ATT_D;
     ushort_t* dv = dqkv + (size_t)b * S * ts + (size_t)(2 * h + hh) * ATT_D;
     att_store_rows16x2(dk, dv, ts, kacc, vacc, ktok_base, S, lm, lg);
+    if constexpr (DBIAS) {
+      att_colsum_rows16(ck, kacc, ktok_base, S, lg);
+      att_colsum_rows16(cv, vacc, ktok_base, S, lg);
+    }
+  }
+  if constexpr (DBIAS) {
+    float* wsum = (float*)lds_at(lds, 32768);
+    att_colsum_wave(ck);
+    att_colsum_wave(cv);
+    if (lg == 0) {
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        wsum[w * 128 + ct * 16 + lm] = ck[ct];
+        wsum[w * 128 + 64 + ct * 16 + lm] = cv[ct];
+      }
+    }
+    __syncthreads();
+    if (tid < 128) {
+      const int QB = (S + 63) / 64;
+      // tid < 64: dK column tid; otherwise dV column tid - 64
+      const size_t col = (size_t)((tid < 64 ? h : 2 * h) + hh) * ATT_D + (tid & 63);
+      float* dst = dbscr + (size_t)b * QB * ts + col;
+      dst[0] = (wsum[tid] + wsum[128 + tid]) + (wsum[256 + tid] + wsum[384 + tid]);
+      for (int q = 1; q < QB; ++q) dst[(size_t)q * ts] = 0.f;
+    }
   }
 }
 
@@ -490,6 +546,28 @@ SKY_EXPORT int sky_attn_bwd_fused(uint64_t stream, uint64_t qkv,
   return 0;
 }
 
+// the bwd1s + bwd2 pair; DBIAS also fills the column-partial scratch
+template <bool DBIAS>
+static void launch_attn_bwd_pair(hipStream_t s, uint64_t qkv, uint64_t dout,
+                                 uint64_t mask, uint64_t m, uint64_t lsum,
+                                 uint64_t pdT, uint64_t dsT, uint64_t dqkv,
+                                 int64_t B, int64_t S, int64_t h, float scale,
+                                 float keep, uint64_t salt, uint64_t state,
+                                 float* dbscr) {
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  ATT_LAUNCH_HM(mask != 0, (attn_bwd1s_kernel<HM, DBIAS>), grid, 48 * 1024, s,
+                (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
+                (ushort_t*)pdT, (ushort_t*)dsT, (ushort_t*)dqkv, (int)B,
+                (int)S, (int)h, scale, keep, salt,
+                (const unsigned long long*)state, dbscr);
+  hipLaunchKernelGGL(attn_bwd2_kernel<DBIAS>, dim3((unsigned)(B * h)),
+                     dim3(256), (DBIAS ? 34 : 32) * 1024, s,
+                     (const ushort_t*)qkv, (const ushort_t*)dout,
+                     (const ushort_t*)pdT, (const ushort_t*)dsT,
+                     (ushort_t*)dqkv, (int)B, (int)S, (int)h, dbscr);
+}
+
 SKY_EXPORT int sky_attn_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
                             uint64_t mask, uint64_t m, uint64_t lsum,
                             uint64_t pdT, uint64_t dsT, uint64_t dqkv,
@@ -497,19 +575,32 @@ SKY_EXPORT int sky_attn_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
                             float scale, float keep, uint64_t salt,
                             uint64_t state) {
   if (d != ATT_D || S > ATT_SMAX) return (int)hipErrorInvalidValue;
+  launch_attn_bwd_pair<false>((hipStream_t)stream, qkv, dout, mask, m, lsum,
+                              pdT, dsT, dqkv, B, S, h, scale, keep, salt,
+                              state, nullptr);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// sky_attn_bwd that also returns dbias[3*h*64] = the column sums of dqkv
+// over its B*S rows, i.e. the bias gradient of the linear that produced
+// qkv, taken from the kernels' registers instead of a re-read of dqkv.
+// scratch: fp32 [B * ceil(S/64)][3*h*64], no memset needed; dbias_dt is
+// the DT_* tag of the dbias buffer.
+SKY_EXPORT int sky_attn_bwd_dbias(uint64_t stream, uint64_t qkv, uint64_t dout,
+                                  uint64_t mask, uint64_t m, uint64_t lsum,
+                                  uint64_t pdT, uint64_t dsT, uint64_t dqkv,
+                                  int64_t B, int64_t S, int64_t h, int64_t d,
+                                  float scale, float keep, uint64_t salt,
+                                  uint64_t state, uint64_t scratch,
+                                  uint64_t dbias, int dbias_dt) {
+  if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
+    return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
-  ATT_LAUNCH_HM(mask != 0, (attn_bwd1s_kernel<HM>), grid, 48 * 1024, s,
-                (const ushort_t*)qkv, (const ushort_t*)dout,
-                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
-                (ushort_t*)pdT, (ushort_t*)dsT, (ushort_t*)dqkv, (int)B,
-                (int)S, (int)h, scale, keep, salt,
-                (const unsigned long long*)state);
-  hipLaunchKernelGGL(attn_bwd2_kernel, dim3((unsigned)(B * h)), dim3(256),
-                     32 * 1024, s, (const ushort_t*)qkv,
-                     (const ushort_t*)dout, (const ushort_t*)pdT,
-                     (const ushort_t*)dsT, (ushort_t*)dqkv, (int)B, (int)S,
-                     (int)h);
+  launch_attn_bwd_pair<true>(s, qkv, dout, mask, m, lsum, pdT, dsT, dqkv, B, S,
+                             h, scale, keep, salt, state, (float*)scratch);
+  sky_launch_colsum_final(s, (const float*)scratch, (void*)dbias,
+                          3 * h * ATT_D, B * ((S + 63) / 64), dbias_dt);
   LAUNCH_CHECK();
   return 0;
 }

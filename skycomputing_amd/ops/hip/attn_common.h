@@ -187,6 +187,30 @@ DEV void att_store_rows16x2(ushort_t* __restrict__ d0,
   }
 }
 
+// Column sums of a stored 16-row x 64-col tile, for the bias gradient of
+// the linear that produced the tile's tensor: cs[ct] += over the lane's 4
+// rows (rows < S only) of the value AS att_store_rows16 STORES IT (rounded
+// to bf16), so the sum is over exactly what the weight-gradient GEMM reads.
+DEV void att_colsum_rows16(float (&cs)[4], const f32x4 (&acc)[4], int row0,
+                           int S, int lg) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (row0 + lg * 4 + r < S) cs[ct] += bf16_to_f32(f32_to_bf16(acc[ct][r]));
+  }
+}
+
+// Fold the four lg row groups of a wave: afterwards every lane holds the
+// wave's sum for its column ct*16 + lm.
+DEV void att_colsum_wave(float (&cs)[4]) {
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    cs[ct] += __shfl_xor(cs[ct], 16, 64);
+    cs[ct] += __shfl_xor(cs[ct], 32, 64);
+  }
+}
+
 // Launch KERNEL, an expression in the constexpr bool HM such as
 // (attn_bwd1s_kernel<HM>), as its HAS_MASK instantiation picked by the
 // runtime bool has_mask; 256 threads, the argument list written once.

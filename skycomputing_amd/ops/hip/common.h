@@ -172,6 +172,12 @@ DEV float gelu_grad_f(float x) {
   return cdf + x * pdf;
 }
 
+// Slab reduction shared by the two-stage column sums (defined in
+// elementwise.hip): out[c] = sum over the nslabs rows of the fp32 scratch
+// [nslabs][cols], written as dtout (a DT_* tag). One launch.
+void sky_launch_colsum_final(hipStream_t s, const float* scratch, void* out,
+                             int64_t cols, int64_t nslabs, int dtout);
+
 #define LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 #define SKY_EXPORT extern "C" __attribute__((visibility("default")))

@@ -224,6 +224,17 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(
   if (g == 0 && col < cols) store_elem<DTOUT>(out, col, lds[0][c]);
 }
 
+void sky_launch_colsum_final(hipStream_t s, const float* scratch, void* out,
+                             int64_t cols, int64_t nslabs, int dtout) {
+  dim3 g2((unsigned)((cols + 15) / 16));
+  if (dtout == DT_BF16)
+    hipLaunchKernelGGL((colsum_final_kernel<256, DT_BF16>), g2, dim3(1024), 0,
+                       s, scratch, out, cols, nslabs);
+  else
+    hipLaunchKernelGGL((colsum_final_kernel<256, DT_F32>), g2, dim3(1024), 0,
+                       s, scratch, out, cols, nslabs);
+}
+
 template <int DT, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void colsum_kernel(
     const void* __restrict__ src, float* __restrict__ out, int64_t rows,
@@ -259,13 +270,7 @@ static void launch_colsum(hipStream_t s, const void* src, void* out,
     dim3 grid((unsigned)gx, (unsigned)nslabs);
     hipLaunchKernelGGL((colsum_part_kernel<DT, BLOCK>), grid, dim3(BLOCK), 0,
                        s, src, scratch, rows, cols8, slab);
-    dim3 g2((unsigned)((cols + 15) / 16));
-    if (dtout == DT_BF16)
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_BF16>), g2, dim3(1024), 0,
-                         s, scratch, out, cols, nslabs);
-    else
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_F32>), g2, dim3(1024), 0,
-                         s, scratch, out, cols, nslabs);
+    sky_launch_colsum_final(s, scratch, out, cols, nslabs, dtout);
     return;
   }
   constexpr int BLOCK = 256;
@@ -326,13 +331,7 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     else
       hb ? launch_cs(bias_gelu_bwd_cs_kernel<DT_BF16, true>)
          : launch_cs(bias_gelu_bwd_cs_kernel<DT_BF16, false>);
-    dim3 g2((unsigned)((cols + 15) / 16));
-    if (dt == DT_BF16)
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_BF16>), g2, dim3(1024),
-                         0, s, (float*)scratch, (void*)db, cols, nslabs);
-    else
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_F32>), g2, dim3(1024),
-                         0, s, (float*)scratch, (void*)db, cols, nslabs);
+    sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
     LAUNCH_CHECK();
     return 0;
   }
@@ -362,13 +361,7 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     else
       hb ? launch_part(bias_gelu_bwd_part_kernel<DT_BF16, true, BLOCK>)
          : launch_part(bias_gelu_bwd_part_kernel<DT_BF16, false, BLOCK>);
-    dim3 g2((unsigned)((cols + 15) / 16));
-    if (dt == DT_BF16)
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_BF16>), g2, dim3(1024),
-                         0, s, (float*)scratch, (void*)db, cols, nslabs);
-    else
-      hipLaunchKernelGGL((colsum_final_kernel<256, DT_F32>), g2, dim3(1024),
-                         0, s, (float*)scratch, (void*)db, cols, nslabs);
+    sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
     LAUNCH_CHECK();
     return 0;
   }

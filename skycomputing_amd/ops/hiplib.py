@@ -77,6 +77,9 @@ def _register_signatures(lib):
         #                      strm qkv mask out  m    l    B    S    h    d scale keep salt state
         "sky_attn_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout mask m l pdT dsT dqkv | B S h d scale keep salt state
+        "sky_attn_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        # sky_attn_bwd's arguments + scratch (fp32 [B*ceil(S/64)][3*h*d]),
+        # dbias [3*h*d] (column sum of dqkv as stored), dbias dt
         "sky_attn_bwd_fused": [u64] * 7 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout mask m l dqkv | B S h d scale keep salt state
         # (ONE kernel: dQ/dK/dV, P+dS never leave LDS)

@@ -18,6 +18,27 @@
 
 // ---------------- forward (vectorized, wave per row) ----------------
 
+// 64-lane sum through DPP row shifts and row broadcasts (VALU only) instead
+// of wave_sum's six dependent LDS-crossbar shuffles. The forward needs its
+// two sums one after the other (mean, then the centred squares), so the
+// reduction's latency is on the critical path twice. Lanes a shift has no
+// source for, and rows a broadcast is masked off for, add 0.
+template <int CTRL, int ROW_MASK>
+DEV float dpp_add(float v) {
+  const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL,
+                                            ROW_MASK, 0xf, true);
+  return v + __int_as_float(t);
+}
+DEV float wave_sum_dpp(float v) {
+  v = dpp_add<0x111, 0xf>(v);  // row_shr:1
+  v = dpp_add<0x112, 0xf>(v);  // row_shr:2
+  v = dpp_add<0x114, 0xf>(v);  // row_shr:4
+  v = dpp_add<0x118, 0xf>(v);  // row_shr:8 -> lane 15 of a row: the row's sum
+  v = dpp_add<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+  v = dpp_add<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
 // DROP: apply dropout to x BEFORE the residual add (the BERT pattern
 // LN(dropout(dense(x)) + residual), reference bert_layers.py:283-288);
 // the mask is regenerated from (salt,state,element index) in backward.
@@ -39,7 +60,7 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
   for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows;
        row += (int64_t)gridDim.x * 4) {
     const int64_t base8 = row * cols8;
-    float s = 0.f, s2 = 0.f;
+    float s = 0.f;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       const int64_t i8 = (int64_t)c * WAVE + lane;
@@ -63,13 +84,28 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
           for (int j = 0; j < 8; ++j) v[c][j] += r[j];
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s += v[c][j]; s2 += v[c][j] * v[c][j]; }
+        for (int j = 0; j < 8; ++j) s += v[c][j];
       }
     }
-    s = wave_sum(s);
-    s2 = wave_sum(s2);
+    s = wave_sum_dpp(s);
     const float mean = s / (float)cols;
-    const float rstd = rsqrtf(fmaxf(s2 / (float)cols - mean * mean, 0.f) + eps);
+    // variance from centred values: E[x^2] - mean^2 cancels to nothing
+    // once |mean| >> std (fp32 x-hat error 2.4e-3 at mean 64, std 1); the
+    // row is in registers, so the second pass costs no memory traffic
+    float s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int64_t i8 = (int64_t)c * WAVE + lane;
+      if (i8 < cols8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float d = v[c][j] - mean;
+          s2 += d * d;
+        }
+      }
+    }
+    s2 = wave_sum_dpp(s2);
+    const float rstd = rsqrtf(s2 / (float)cols + eps);
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
@@ -97,23 +133,41 @@ __global__ __launch_bounds__(BLOCK) void ln_fwd_kernel(
   __shared__ float lds[BLOCK / WAVE > 2 ? BLOCK / WAVE : 2];
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const int64_t base = row * cols;
-    float s = 0.f, s2 = 0.f;
+    float s = 0.f;
     for (int64_t c = threadIdx.x; c < cols; c += BLOCK) {
       float v = load_elem<DT>(x, base + c);
       if (HAS_RES) v += load_elem<DT>(res, base + c);
       s += v;
-      s2 += v * v;
     }
     s = block_sum<BLOCK>(s, lds);
-    s2 = block_sum<BLOCK>(s2, lds);
     const float mean = s / (float)cols;
-    const float rstd = rsqrtf(fmaxf(s2 / (float)cols - mean * mean, 0.f) + eps);
+    // centred variance (see ln_fwd_vec_kernel); the row is re-read anyway.
+    // The centred values also sum to what rounding left out of `mean`
+    // (delta, up to half an ulp of the mean: 4e-6 at 64, too small to
+    // change the stored mean). This path is on no hot loop, so it spends a
+    // third block_sum to take delta off x - mean, which keeps y at fp32
+    // relative accuracy for any row mean; the vector kernel stays at the
+    // two-pass accuracy of its two reductions.
+    float s1 = 0.f, s2 = 0.f;
+    for (int64_t c = threadIdx.x; c < cols; c += BLOCK) {
+      float v = load_elem<DT>(x, base + c);
+      if (HAS_RES) v += load_elem<DT>(res, base + c);
+      const float d = v - mean;
+      s1 += d;
+      s2 += d * d;
+    }
+    s1 = block_sum<BLOCK>(s1, lds);
+    s2 = block_sum<BLOCK>(s2, lds);
+    const float delta = s1 / (float)cols;
+    const float rstd =
+        rsqrtf(fmaxf(s2 / (float)cols - delta * delta, 0.f) + eps);
     if (threadIdx.x == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
     for (int64_t c = threadIdx.x; c < cols; c += BLOCK) {
       float v = load_elem<DT>(x, base + c);
       if (HAS_RES) v += load_elem<DT>(res, base + c);
       store_elem<DT>(y, base + c,
-                     (v - mean) * rstd * load_elem<DT>(w, c) + load_elem<DT>(b, c));
+                     ((v - mean) - delta) * rstd * load_elem<DT>(w, c) +
+                         load_elem<DT>(b, c));
     }
   }
 }

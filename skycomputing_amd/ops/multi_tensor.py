@@ -3,8 +3,8 @@
 Packs per-parameter {param, grad, master, momentum} pointers into a device
 descriptor array (one entry per <=1M-element slab) so the whole stage
 updates in ONE kernel launch (ops/hip/sgd.hip). The plan is rebuilt only
-when a grad tensor's identity changes (autograd reuses .grad buffers, so in
-steady state this is built once).
+when one of those pointers changes (autograd reuses .grad buffers and the
+optimizer owns the rest, so in steady state this is built once).
 """
 
 from __future__ import annotations
@@ -48,9 +48,24 @@ def _build_plan(params, grads, masters, moms):
     return cpu.to(params[0].device, non_blocking=True), len(rows)
 
 
+def _plan_signature(params, grads, masters, moms) -> tuple:
+    """Every pointer (and count) a descriptor is built from. A parameter
+    that gets new storage (``p.data = ...``, a checkpoint restore) keeps
+    its ``.grad`` buffer, so grad pointers alone would leave the cached
+    descriptors writing the old storage."""
+    sig = [_SLAB]
+    for group in (params, grads, masters, moms):
+        if group is None:
+            sig.append(None)
+        else:
+            sig.extend(t.data_ptr() for t in group)
+    sig.extend(p.numel() for p in params)
+    return tuple(sig)
+
+
 def multi_tensor_sgd(params, grads, masters, moms, lr, momentum, wd):
     key = id(params)
-    sig = tuple(g.data_ptr() for g in grads)
+    sig = _plan_signature(params, grads, masters, moms)
     cached = _PLAN_CACHE.get(key)
     if cached is None or cached[0] != sig:
         desc, n = _build_plan(params, grads, masters, moms)

@@ -705,6 +705,9 @@ def test_gemm2_linear_fwd_bwd_matches_reference():
         assert torch.allclose(y.float(), yr, atol=0.5, rtol=0.05)
         assert torch.allclose(x.grad.float(), xf.grad, atol=0.5, rtol=0.05)
         assert torch.allclose(w.grad.float(), wf.grad, atol=1.0, rtol=0.05)
+        # db of the b == 0 form of sky_bias_gelu_bwd (the benchmark's path)
+        assert torch.allclose(b.grad.float(), bf.grad, atol=2.0, rtol=0.05), (
+            (b.grad.float() - bf.grad).abs().max())
     finally:
         F._G2_SITES = old
 

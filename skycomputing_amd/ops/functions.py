@@ -34,7 +34,7 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-_CS_SLABS = 1024  # must match CS_SLABS / LN_SLABS in the HIP sources
+_CS_SLABS = 1024  # MAX_SLABS in ops/hip/common.h
 
 
 def _red_scratch(cols: int, pairs: int, device) -> torch.Tensor:
@@ -60,25 +60,10 @@ class LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps, residual, dropout_p=0.0):
-        lib = hiplib.require()
         x = x.contiguous()
         residual = residual.contiguous() if residual is not None else None
-        cols = x.shape[-1]
-        rows = x.numel() // cols
-        y = torch.empty_like(x)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         keep = 1.0 - dropout_p
-        salt = _next_seed() if keep < 1.0 else 0
-        state_ptr = rng_state().data_ptr() if keep < 1.0 else 0
-        check(
-            lib.sky_layernorm_fwd(
-                _stream(), ptr(x), ptr(residual), ptr(weight), ptr(bias),
-                ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, _dt(x),
-                keep, salt, state_ptr,
-            ),
-            "sky_layernorm_fwd",
-        )
+        y, mean, rstd, salt = _ln_fwd(x, residual, weight, bias, eps, keep)
         ctx.save_for_backward(x, weight, mean, rstd)
         ctx.residual = residual
         ctx.has_residual = residual is not None
@@ -87,44 +72,30 @@ class LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = hiplib.require()
         x, weight, mean, rstd = ctx.saved_tensors
         dy = dy.contiguous()
         cols = x.shape[-1]
-        rows = x.numel() // cols
+        if cols % 8 == 0:
+            dx, dw, db, _, dgrad_res = _ln_bwd(
+                dy, x, ctx.residual, weight, mean, rstd, ctx.keep, ctx.salt,
+                xsum=False)
+            return dx, dw, db, None, dgrad_res, None
+        # odd widths: scalar kernels, dw/db through fp32 atomics; the kernels
+        # refuse dropout there, so the residual's gradient is dx itself
         dx = torch.empty_like(x)
-        fast = cols % 8 == 0
-        if fast:
-            # the final reduction stage writes the param dtype directly
-            dw = torch.empty(cols, dtype=weight.dtype, device=x.device)
-            db = torch.empty(cols, dtype=weight.dtype, device=x.device)
-            scratch = _red_scratch(cols, 2, x.device)
-        else:
-            dw = torch.zeros(cols, dtype=torch.float32, device=x.device)
-            db = torch.zeros(cols, dtype=torch.float32, device=x.device)
-            scratch = None
-        drop = ctx.keep < 1.0
-        dres = torch.empty_like(x) if (drop and ctx.has_residual) else None
-        state_ptr = rng_state().data_ptr() if drop else 0
+        dw = torch.zeros(cols, dtype=torch.float32, device=x.device)
+        db = torch.zeros(cols, dtype=torch.float32, device=x.device)
         check(
-            lib.sky_layernorm_bwd(
+            hiplib.require().sky_layernorm_bwd(
                 _stream(), ptr(dy), ptr(x), ptr(ctx.residual), ptr(weight),
-                ptr(mean), ptr(rstd), ptr(dx), ptr(dw), ptr(db),
-                ptr(scratch), rows, cols, _dt(x), ctx.keep, ctx.salt,
-                state_ptr, ptr(dres),
+                ptr(mean), ptr(rstd), ptr(dx), ptr(dw), ptr(db), 0,
+                x.numel() // cols, cols, _dt(x), ctx.keep, ctx.salt,
+                rng_state().data_ptr() if ctx.keep < 1.0 else 0, 0,
             ),
             "sky_layernorm_bwd",
         )
-        if not fast:
-            dw = dw.to(weight.dtype)
-            db = db.to(weight.dtype)
-        if not ctx.has_residual:
-            dgrad_res = None
-        elif drop:
-            dgrad_res = dres
-        else:
-            dgrad_res = dx
-        return dx, dw, db, None, dgrad_res, None
+        return (dx, dw.to(weight.dtype), db.to(weight.dtype), None,
+                dx if ctx.has_residual else None, None)
 
 
 class BiasGeluFn(torch.autograd.Function):
@@ -723,8 +694,7 @@ class LinearBiasFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, weight.shape[0])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
-        dx = gemm2_dgrad(dy2, weight)
-        dx = dx.view(ctx.xshape) if dx is not None else dy2.mm(weight).view(ctx.xshape)
+        dx = _dgrad(dy2, weight).view(ctx.xshape)
         dw2 = gemm2_wgrad(dy2, x2 if x2.is_contiguous() else x2.contiguous())
         if dw2 is not None:
             db = colsum(dy2, weight.dtype) if ctx.has_bias else None
@@ -778,29 +748,31 @@ def _ln_fwd(h, residual, ln_w, ln_b, eps, keep):
     return y, mean, rstd, salt
 
 
-def _ln_bwd_xsum(dy, h, residual, ln_w, mean, rstd, keep, salt):
-    """sky_layernorm_bwd_xsum: returns (dh, d_ln_w, d_ln_b, dxsum, dres)
-    with dxsum the column sum of dh as stored and dres the residual's
+def _ln_bwd(dy, h, residual, ln_w, mean, rstd, keep, salt, xsum):
+    """sky_layernorm_bwd (or, with xsum, sky_layernorm_bwd_xsum) for
+    cols % 8 == 0, where the final reduction stage writes the param dtype
+    directly. Returns (dh, d_ln_w, d_ln_b, dxsum, dres) with dxsum the
+    column sum of dh as stored (None without xsum) and dres the residual's
     gradient (dh itself without dropout, None without a residual)."""
+    lib = hiplib.require()
     cols = h.shape[-1]
     rows = h.numel() // cols
     dh = torch.empty_like(h)
     d_ln_w = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-    d_ln_b = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-    dxsum = torch.empty(cols, dtype=ln_w.dtype, device=h.device)
-    scratch = _red_scratch(cols, 3, h.device)
+    d_ln_b = torch.empty_like(d_ln_w)
+    dxsum = torch.empty_like(d_ln_w) if xsum else None
+    scratch = _red_scratch(cols, 3 if xsum else 2, h.device)
     drop = keep < 1.0
     dres = torch.empty_like(h) if (drop and residual is not None) else None
     state_ptr = rng_state().data_ptr() if drop else 0
-    check(
-        hiplib.require().sky_layernorm_bwd_xsum(
-            _stream(), ptr(dy), ptr(h), ptr(residual), ptr(ln_w),
-            ptr(mean), ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b),
-            ptr(scratch), rows, cols, _dt(h), keep, salt,
-            state_ptr, ptr(dres), ptr(dxsum),
-        ),
-        "sky_layernorm_bwd_xsum",
-    )
+    args = (_stream(), ptr(dy), ptr(h), ptr(residual), ptr(ln_w), ptr(mean),
+            ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b), ptr(scratch), rows,
+            cols, _dt(h), keep, salt, state_ptr, ptr(dres))
+    if xsum:
+        check(lib.sky_layernorm_bwd_xsum(*args, ptr(dxsum)),
+              "sky_layernorm_bwd_xsum")
+    else:
+        check(lib.sky_layernorm_bwd(*args), "sky_layernorm_bwd")
     if residual is not None and not drop:
         dres = dh
     return dh, d_ln_w, d_ln_b, dxsum, dres
@@ -835,9 +807,9 @@ class LinearResidualLayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, weight, h, ln_w, mean, rstd = ctx.saved_tensors
-        dh, d_ln_w, d_ln_b, dbias, dgrad_res = _ln_bwd_xsum(
+        dh, d_ln_w, d_ln_b, dbias, dgrad_res = _ln_bwd(
             dy.contiguous(), h, ctx.residual, ln_w, mean, rstd, ctx.keep,
-            ctx.salt)
+            ctx.salt, xsum=True)
         if dbias.dtype != weight.dtype:
             dbias = dbias.to(weight.dtype)
         dh2 = dh.view(-1, h.shape[-1])
@@ -900,8 +872,9 @@ class AttentionBlockFn(torch.autograd.Function):
          rstd) = ctx.saved_tensors
         B, S, _, nh, d = qkv.shape
         H = nh * d
-        dh, d_ln_w, d_ln_b, dbo, dres = _ln_bwd_xsum(
-            dy.contiguous(), h, x2, ln_w, mean, rstd, ctx.keep, ctx.salt)
+        dh, d_ln_w, d_ln_b, dbo, dres = _ln_bwd(
+            dy.contiguous(), h, x2, ln_w, mean, rstd, ctx.keep, ctx.salt,
+            xsum=True)
         dh2 = dh.view(-1, H)
         dctx = _dgrad(dh2, wo)
         dwo = _wgrad_plain(dh2, c2, wo)
@@ -990,8 +963,7 @@ class LinearGeluFn(torch.autograd.Function):
             ),
             "sky_bias_gelu_bwd",
         )
-        dx = gemm2_dgrad(dpre, weight)
-        dx = dx.view(ctx.xshape) if dx is not None else dpre.mm(weight).view(ctx.xshape)
+        dx = _dgrad(dpre, weight).view(ctx.xshape)
         dw = gemm2_wgrad(dpre, x2)
         if dw is None:
             dw = dpre.t().mm(x2)

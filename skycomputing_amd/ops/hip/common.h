@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define WAVE 64
 #define DEV __device__ __forceinline__
@@ -141,10 +142,39 @@ DEV float rng_uniform(uint64_t seed, uint64_t idx) {
 // dropout keep decision: one splitmix hash feeds FOUR consecutive indices
 // (16-bit thresholds) — 4x fewer hashes when a lane owns consecutive
 // elements. keep16 = keep * 65536 (keep == 1 -> always true).
+// rng_keep16 (one element) and RNG_DROP8 (a lane's 8) are the two spellings
+// of the LINEAR index scheme: element e keeps iff slice e & 3 of
+// rng_hash(seed, e >> 2) is below keep16.
 DEV bool rng_keep16(uint64_t seed, uint64_t idx, unsigned keep16) {
   uint64_t z = rng_hash(seed, idx >> 2);
   return (unsigned)((z >> (16 * (idx & 3))) & 0xFFFFu) < keep16;
 }
+
+// The same decisions for the 8 consecutive elements 8*i8 .. 8*i8+7 (exactly
+// two hash quads): float v[8] becomes v[j] * inv_keep where kept and 0 where
+// dropped; bit j of the unsigned lvalue `bits` is element j's keep decision.
+//
+// A statement macro, not a function, on purpose. These kernels are compiled
+// with fp contraction on, so which multiplies become FMAs is settled only
+// after the SLP vectoriser has paired the lanes' 8 values, and that pairing
+// changes when this loop reaches the kernel already unrolled, as it does
+// through any inlined function (by pointer, by reference or by value):
+// 49 of layernorm.hip's 112 kernels then compile differently and their
+// outputs move by an ulp (profiles/r06_notes.md). Expanded in place, the
+// kernels' results do not depend on where this text lives.
+#define RNG_DROP8(seed, i8, keep16, inv_keep, v, bits)                        \
+  do {                                                                        \
+    const uint64_t z0_ = rng_hash(seed, (uint64_t)(i8) * 2);                  \
+    const uint64_t z1_ = rng_hash(seed, (uint64_t)(i8) * 2 + 1);              \
+    bits = 0;                                                                 \
+    _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) {                        \
+      const uint64_t zz_ = j_ < 4 ? z0_ : z1_;                                \
+      const bool kb_ =                                                        \
+          (unsigned)((zz_ >> (16 * (j_ & 3))) & 0xFFFFu) < (keep16);          \
+      bits |= (unsigned)kb_ << j_;                                            \
+      (v)[j_] = kb_ ? (v)[j_] * (inv_keep) : 0.f;                             \
+    }                                                                         \
+  } while (0)
 
 DEV unsigned keep_to_16(float keep) {
   return keep >= 1.f ? 0x20000u : (unsigned)(keep * 65536.f + 0.5f);
@@ -177,6 +207,35 @@ DEV float gelu_grad_f(float x) {
 // [nslabs][cols], written as dtout (a DT_* tag). One launch.
 void sky_launch_colsum_final(hipStream_t s, const float* scratch, void* out,
                              int64_t cols, int64_t nslabs, int dtout);
+
+// Most slabs any two-stage column reduction writes: callers size the fp32
+// scratch for MAX_SLABS slabs (ops/functions.py: _CS_SLABS).
+constexpr int MAX_SLABS = 1024;
+
+// Runtime (dt, has_res, drop, ch) -> compile-time tags: calls
+// f(DT, HAS_RES, DROP, CH) with std::integral_constant arguments, usable
+// directly as template arguments. ch (chunks of 512 elements per row) picks
+// CH = 2, 4 or 8; a ch above MAXCH launches nothing (the caller has checked
+// the width). Callers without a dropout or chunk axis pass false / 0 and
+// ignore the tag.
+template <int MAXCH = 8, class F>
+static inline void dispatch_tags(int dt, bool has_res, bool drop, int ch,
+                                 F&& f) {
+  using std::integral_constant;
+  auto by_ch = [&](auto DT, auto HR, auto DR) {
+    if (ch <= 2) f(DT, HR, DR, integral_constant<int, 2>{});
+    else if (ch <= 4) f(DT, HR, DR, integral_constant<int, 4>{});
+    else if constexpr (MAXCH >= 8) f(DT, HR, DR, integral_constant<int, 8>{});
+  };
+  auto by_flags = [&](auto DT) {
+    if (has_res) drop ? by_ch(DT, std::true_type{}, std::true_type{})
+                      : by_ch(DT, std::true_type{}, std::false_type{});
+    else drop ? by_ch(DT, std::false_type{}, std::true_type{})
+              : by_ch(DT, std::false_type{}, std::false_type{});
+  };
+  if (dt == DT_F32) by_flags(integral_constant<int, DT_F32>{});
+  else by_flags(integral_constant<int, DT_BF16>{});
+}
 
 #define LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 

@@ -174,8 +174,6 @@ __global__ __launch_bounds__(256) void bias_gelu_bwd_cs_kernel(
 // no zero-init: stage 1 writes per-slab partials [nslabs][cols] fp32 to a
 // scratch buffer (thread owns 8 consecutive columns, 16 B loads); stage 2
 // reduces the slab axis and WRITES the result.
-#define CS_SLABS 1024
-
 template <int DT, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void colsum_part_kernel(
     const void* __restrict__ src, float* __restrict__ scratch, int64_t rows,
@@ -248,7 +246,7 @@ __global__ __launch_bounds__(BLOCK) void colsum_kernel(
   atomicAdd(&out[col], s);
 }
 
-// scratch must hold CS_SLABS * cols floats when the fast path is taken
+// scratch must hold MAX_SLABS * cols floats when the fast path is taken
 // (cols % 8 == 0); pass scratch = nullptr to force the atomic fallback
 // (out must then be pre-zeroed).
 template <int DT>
@@ -264,7 +262,7 @@ static void launch_colsum(hipStream_t s, const void* src, void* out,
     const int64_t gx = (cols8 + BLOCK - 1) / BLOCK;
     int64_t nslabs = 1024 / gx;
     if (nslabs < 128) nslabs = 128;
-    if (nslabs > CS_SLABS) nslabs = CS_SLABS;
+    if (nslabs > MAX_SLABS) nslabs = MAX_SLABS;
     if (nslabs > rows) nslabs = rows;
     const int64_t slab = (rows + nslabs - 1) / nslabs;
     dim3 grid((unsigned)gx, (unsigned)nslabs);
@@ -316,7 +314,7 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     // scratch re-read (A/B'd: 1024 slabs put 16 MB on the final)
     int64_t nslabs = 1024 / nwin;
     if (const char* e = getenv("SKY_GELU_CS_SLABS")) nslabs = atoll(e);
-    if (nslabs > CS_SLABS) nslabs = CS_SLABS;
+    if (nslabs > MAX_SLABS) nslabs = MAX_SLABS;
     if (nslabs > rows) nslabs = rows;
     const int64_t slab = (rows + nslabs - 1) / nslabs;
     dim3 grid((unsigned)(nwin * nslabs));
@@ -325,12 +323,9 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
                          (const void*)x, (const void*)b, (void*)dx,
                          (float*)scratch, rows, cols8, slab);
     };
-    if (dt == DT_F32)
-      hb ? launch_cs(bias_gelu_bwd_cs_kernel<DT_F32, true>)
-         : launch_cs(bias_gelu_bwd_cs_kernel<DT_F32, false>);
-    else
-      hb ? launch_cs(bias_gelu_bwd_cs_kernel<DT_BF16, true>)
-         : launch_cs(bias_gelu_bwd_cs_kernel<DT_BF16, false>);
+    dispatch_tags(dt, hb, false, 0, [&](auto DT, auto HB, auto, auto) {
+      launch_cs(bias_gelu_bwd_cs_kernel<DT, HB>);
+    });
     sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
     LAUNCH_CHECK();
     return 0;
@@ -346,7 +341,7 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     const int64_t gx = (cols8 + BLOCK - 1) / BLOCK;
     int64_t nslabs = 4096 / gx;
     if (nslabs < 128) nslabs = 128;
-    if (nslabs > CS_SLABS) nslabs = CS_SLABS;
+    if (nslabs > MAX_SLABS) nslabs = MAX_SLABS;
     if (nslabs > rows) nslabs = rows;
     const int64_t slab = (rows + nslabs - 1) / nslabs;
     dim3 grid((unsigned)gx, (unsigned)nslabs);
@@ -355,12 +350,9 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
                          (const void*)x, (const void*)b, (void*)dx,
                          (float*)scratch, rows, cols8, slab);
     };
-    if (dt == DT_F32)
-      hb ? launch_part(bias_gelu_bwd_part_kernel<DT_F32, true, BLOCK>)
-         : launch_part(bias_gelu_bwd_part_kernel<DT_F32, false, BLOCK>);
-    else
-      hb ? launch_part(bias_gelu_bwd_part_kernel<DT_BF16, true, BLOCK>)
-         : launch_part(bias_gelu_bwd_part_kernel<DT_BF16, false, BLOCK>);
+    dispatch_tags(dt, hb, false, 0, [&](auto DT, auto HB, auto, auto) {
+      launch_part(bias_gelu_bwd_part_kernel<DT, HB, BLOCK>);
+    });
     sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
     LAUNCH_CHECK();
     return 0;
@@ -373,12 +365,9 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
       hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const void*)dy,
                          (const void*)x, (const void*)b, (void*)dx, n8, cols / 8);
     };
-    if (dt == DT_F32)
-      hb ? launch_vec(bias_gelu_bwd_dx_vec_kernel<DT_F32, true>)
-         : launch_vec(bias_gelu_bwd_dx_vec_kernel<DT_F32, false>);
-    else
-      hb ? launch_vec(bias_gelu_bwd_dx_vec_kernel<DT_BF16, true>)
-         : launch_vec(bias_gelu_bwd_dx_vec_kernel<DT_BF16, false>);
+    dispatch_tags(dt, hb, false, 0, [&](auto DT, auto HB, auto, auto) {
+      launch_vec(bias_gelu_bwd_dx_vec_kernel<DT, HB>);
+    });
   } else {
     unsigned grid = (unsigned)((n + 255) / 256);
     if (grid > 2048u) grid = 2048u;
@@ -386,12 +375,9 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
       hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const void*)dy,
                          (const void*)x, (const void*)b, (void*)dx, n, cols);
     };
-    if (dt == DT_F32)
-      hb ? launch_sc(bias_gelu_bwd_dx_kernel<DT_F32, true>)
-         : launch_sc(bias_gelu_bwd_dx_kernel<DT_F32, false>);
-    else
-      hb ? launch_sc(bias_gelu_bwd_dx_kernel<DT_BF16, true>)
-         : launch_sc(bias_gelu_bwd_dx_kernel<DT_BF16, false>);
+    dispatch_tags(dt, hb, false, 0, [&](auto DT, auto HB, auto, auto) {
+      launch_sc(bias_gelu_bwd_dx_kernel<DT, HB>);
+    });
   }
   if (dt == DT_F32)
     launch_colsum<DT_F32>(s, (const void*)dx, (void*)db, (float*)scratch, rows, cols, dt);
@@ -422,15 +408,8 @@ __global__ __launch_bounds__(256) void dropout_vec_kernel(
        i8 += (int64_t)gridDim.x * 256) {
     float v[8];
     Vec8<DT>::load(x, i8, v);
-    // 8 consecutive elements = exactly 2 hash quads
-    const uint64_t z0 = rng_hash(seed, (uint64_t)i8 * 2);
-    const uint64_t z1 = rng_hash(seed, (uint64_t)i8 * 2 + 1);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint64_t z = j < 4 ? z0 : z1;
-      bool k = (unsigned)((z >> (16 * (j & 3))) & 0xFFFFu) < keep16;
-      v[j] = k ? v[j] * inv_keep : 0.f;
-    }
+    [[maybe_unused]] unsigned kbits;
+    RNG_DROP8(seed, i8, keep16, inv_keep, v, kbits);
     Vec8<DT>::store(y, i8, v);
   }
 }

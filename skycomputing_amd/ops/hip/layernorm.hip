@@ -39,9 +39,38 @@ DEV float wave_sum_dpp(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// DROP: apply dropout to x BEFORE the residual add (the BERT pattern
-// LN(dropout(dense(x)) + residual), reference bert_layers.py:283-288);
-// the mask is regenerated from (salt,state,element index) in backward.
+// Per-launch dropout constants of the vectorized kernels.
+struct LnDrop {
+  uint64_t seed;
+  unsigned keep16;
+  float inv_keep;
+  DEV LnDrop(bool drop, float keep, uint64_t salt,
+             const unsigned long long* state)
+      : seed(drop ? rng_seed(salt, state) : 0),
+        keep16(keep_to_16(keep)),
+        inv_keep(1.f / keep) {}
+};
+
+// A lane's 8 values of the LayerNorm input xs = dropout(x) + res at vec8
+// index i8 (LINEAR scheme: row * cols8 + column vec8). Dropout is applied
+// BEFORE the residual add (the BERT pattern LN(dropout(dense(x)) + residual),
+// reference bert_layers.py:283-288). Fills float v[8]; with DROP also sets
+// the unsigned lvalue kbits to the 8 keep bits, from which the backward
+// masks dx. Reads the enclosing kernel's DT, HAS_RES and DROP, and is a
+// statement macro for RNG_DROP8's reason (ops/hip/common.h).
+#define LN_LOAD_ROW(x, res, i8, drop, v, kbits)                               \
+  do {                                                                        \
+    Vec8<DT>::load(x, i8, v);                                                 \
+    if (DROP)                                                                 \
+      RNG_DROP8((drop).seed, i8, (drop).keep16, (drop).inv_keep, v, kbits);   \
+    if (HAS_RES) {                                                            \
+      float r_[8];                                                            \
+      Vec8<DT>::load(res, i8, r_);                                            \
+      _Pragma("unroll") for (int k_ = 0; k_ < 8; ++k_) (v)[k_] += r_[k_];     \
+    }                                                                         \
+  } while (0)
+
+// DROP: the mask is regenerated from (salt,state,element index) in backward.
 template <int DT, bool HAS_RES, bool DROP, int CH>
 __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
     const void* __restrict__ x, const void* __restrict__ res,
@@ -52,10 +81,7 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const int64_t cols8 = cols / 8;
-  const uint64_t seed =
-      DROP ? rng_seed(salt, state) : 0;
-  const unsigned keep16 = keep_to_16(keep);
-  const float inv_keep = 1.f / keep;
+  const LnDrop drop(DROP, keep, salt, state);
   float v[CH][8];
   for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows;
        row += (int64_t)gridDim.x * 4) {
@@ -65,24 +91,8 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(
     for (int c = 0; c < CH; ++c) {
       const int64_t i8 = (int64_t)c * WAVE + lane;
       if (i8 < cols8) {
-        Vec8<DT>::load(x, base8 + i8, v[c]);
-        if (DROP) {
-          const uint64_t e8 = (uint64_t)(base8 + i8);
-          const uint64_t z0 = rng_hash(seed, e8 * 2);
-          const uint64_t z1 = rng_hash(seed, e8 * 2 + 1);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const uint64_t zz = j < 4 ? z0 : z1;
-            bool kb = (unsigned)((zz >> (16 * (j & 3))) & 0xFFFFu) < keep16;
-            v[c][j] = kb ? v[c][j] * inv_keep : 0.f;
-          }
-        }
-        if (HAS_RES) {
-          float r[8];
-          Vec8<DT>::load(res, base8 + i8, r);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[c][j] += r[j];
-        }
+        [[maybe_unused]] unsigned kbits;
+        LN_LOAD_ROW(x, res, base8 + i8, drop, v[c], kbits);
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += v[c][j];
       }
@@ -176,6 +186,11 @@ static inline bool ln_fast_ok(int64_t cols) {
   return (cols % 8 == 0) && cols <= 64 * 8 * LN_MAXCH;
 }
 
+// chunks of 512 elements (one vec8 per lane) a wave needs for a row
+static inline int ln_chunks(int64_t cols) {
+  return (int)((cols / 8 + WAVE - 1) / WAVE);
+}
+
 SKY_EXPORT int sky_layernorm_fwd(uint64_t stream, uint64_t x, uint64_t res,
                                  uint64_t w, uint64_t b, uint64_t y,
                                  uint64_t mean, uint64_t rstd, int64_t rows,
@@ -188,36 +203,22 @@ SKY_EXPORT int sky_layernorm_fwd(uint64_t stream, uint64_t x, uint64_t res,
   if (ln_fast_ok(cols)) {
     unsigned grid = (unsigned)((rows + 3) / 4);
     if (grid > 8192u) grid = 8192u;
-    const int ch = (int)((cols / 8 + WAVE - 1) / WAVE);
-#define LNFV(DT, HR, DR, CH)                                                  \
-  hipLaunchKernelGGL((ln_fwd_vec_kernel<DT, HR, DR, CH>), dim3(grid),         \
-                     dim3(256), 0, s, (const void*)x, (const void*)res,       \
-                     (const void*)w, (const void*)b, (void*)y, (float*)mean,  \
-                     (float*)rstd, rows, cols, eps, keep, salt,               \
-                     (const unsigned long long*)state)
-#define LNFV_CH(DT, HR, DR)                                                   \
-  do {                                                                        \
-    if (ch <= 2) LNFV(DT, HR, DR, 2);                                         \
-    else if (ch <= 4) LNFV(DT, HR, DR, 4);                                    \
-    else LNFV(DT, HR, DR, 8);                                                 \
-  } while (0)
-#define LNFV_D(DT, HR)                                                        \
-  do { if (drop) LNFV_CH(DT, HR, true); else LNFV_CH(DT, HR, false); } while (0)
-    if (dt == DT_F32) { if (has_res) LNFV_D(DT_F32, true); else LNFV_D(DT_F32, false); }
-    else              { if (has_res) LNFV_D(DT_BF16, true); else LNFV_D(DT_BF16, false); }
-#undef LNFV_D
-#undef LNFV_CH
-#undef LNFV
+    dispatch_tags(dt, has_res, drop, ln_chunks(cols),
+                  [&](auto DT, auto HR, auto DR, auto CH) {
+      hipLaunchKernelGGL((ln_fwd_vec_kernel<DT, HR, DR, CH>), dim3(grid),
+                         dim3(256), 0, s, (const void*)x, (const void*)res,
+                         (const void*)w, (const void*)b, (void*)y,
+                         (float*)mean, (float*)rstd, rows, cols, eps, keep,
+                         salt, (const unsigned long long*)state);
+    });
   } else {
     dim3 grid((unsigned)(rows < 4096 ? rows : 4096));
-#define LNF(DT, HR)                                                           \
-  hipLaunchKernelGGL((ln_fwd_kernel<DT, 256, HR>), grid, dim3(256), 0, s,     \
-                     (const void*)x, (const void*)res, (const void*)w,        \
-                     (const void*)b, (void*)y, (float*)mean, (float*)rstd,    \
-                     rows, cols, eps)
-    if (dt == DT_F32) { if (has_res) LNF(DT_F32, true); else LNF(DT_F32, false); }
-    else              { if (has_res) LNF(DT_BF16, true); else LNF(DT_BF16, false); }
-#undef LNF
+    dispatch_tags(dt, has_res, false, 0, [&](auto DT, auto HR, auto, auto) {
+      hipLaunchKernelGGL((ln_fwd_kernel<DT, 256, HR>), grid, dim3(256), 0, s,
+                         (const void*)x, (const void*)res, (const void*)w,
+                         (const void*)b, (void*)y, (float*)mean, (float*)rstd,
+                         rows, cols, eps);
+    });
   }
   LAUNCH_CHECK();
   return 0;
@@ -228,97 +229,20 @@ SKY_EXPORT int sky_layernorm_fwd(uint64_t stream, uint64_t x, uint64_t res,
 // dx = rstd * (dxhat - mean_c(dxhat) - xhat * mean_c(dxhat * xhat))
 // dw[c] += sum_r dy * xhat ; db[c] += sum_r dy
 
+// Vectorized dx with NS column sums (0, 2 or 3), wave per row.
+//
 // DROP: x is the PRE-dropout tensor; the mask is regenerated to rebuild
 // xs = dropout(x)+res for the statistics, dx gets the mask/keep factor,
 // and (when dres != null) the residual grad d_xs is written separately.
-template <int DT, bool HAS_RES, bool DROP, int CH>
-__global__ __launch_bounds__(256) void ln_bwd_dx_vec_kernel(
-    const void* __restrict__ dy, const void* __restrict__ x,
-    const void* __restrict__ res, const void* __restrict__ w,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    void* __restrict__ dx, void* __restrict__ dres, int64_t rows,
-    int64_t cols, float keep, uint64_t salt,
-    const unsigned long long* __restrict__ state) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int64_t cols8 = cols / 8;
-  const uint64_t seed =
-      DROP ? rng_seed(salt, state) : 0;
-  const unsigned keep16 = keep_to_16(keep);
-  const float inv_keep = 1.f / keep;
-  float xh[CH][8], dxh[CH][8];
-  unsigned kbits[CH];
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows;
-       row += (int64_t)gridDim.x * 4) {
-    const int64_t base8 = row * cols8;
-    const float mu = mean[row], rs = rstd[row];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const int64_t i8 = (int64_t)c * WAVE + lane;
-      if (i8 < cols8) {
-        float xv[8], dyv[8], wv[8];
-        Vec8<DT>::load(x, base8 + i8, xv);
-        if (DROP) {
-          const uint64_t e8 = (uint64_t)(base8 + i8);
-          const uint64_t z0 = rng_hash(seed, e8 * 2);
-          const uint64_t z1 = rng_hash(seed, e8 * 2 + 1);
-          kbits[c] = 0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const uint64_t zz = j < 4 ? z0 : z1;
-            bool kb = (unsigned)((zz >> (16 * (j & 3))) & 0xFFFFu) < keep16;
-            kbits[c] |= (unsigned)kb << j;
-            xv[j] = kb ? xv[j] * inv_keep : 0.f;
-          }
-        }
-        if (HAS_RES) {
-          float r[8];
-          Vec8<DT>::load(res, base8 + i8, r);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xv[j] += r[j];
-        }
-        Vec8<DT>::load(dy, base8 + i8, dyv);
-        Vec8<DT>::load(w, i8, wv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          xh[c][j] = (xv[j] - mu) * rs;
-          dxh[c][j] = dyv[j] * wv[j];
-          s1 += dxh[c][j];
-          s2 += dxh[c][j] * xh[c][j];
-        }
-      }
-    }
-    s1 = wave_sum(s1) / (float)cols;
-    s2 = wave_sum(s2) / (float)cols;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const int64_t i8 = (int64_t)c * WAVE + lane;
-      if (i8 < cols8) {
-        float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          o[j] = rs * (dxh[c][j] - s1 - xh[c][j] * s2);
-        if (DROP && dres != nullptr) Vec8<DT>::store(dres, base8 + i8, o);
-        if (DROP) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            o[j] = ((kbits[c] >> j) & 1u) ? o[j] * inv_keep : 0.f;
-        }
-        Vec8<DT>::store(dx, base8 + i8, o);
-      }
-    }
-  }
-}
-
-// Fused dx + dw/db column partials: the dx pass already holds dy and xhat
-// in registers for every element, and a wave's lane covers the SAME
-// column slices on every row it processes — so the dw/db partial sums
-// accumulate in registers for free and wb_part's 16-24 MB re-read of
-// dy/x disappears. Each WAVE is one scratch slab (slab = blockIdx*4+wid,
-// no LDS merge); the grid is capped so nslabs <= LN_SLABS.
 //
-// XSUM adds a third column partial: the sum over rows of the value stored
+// NS = 2 fuses the dw/db column partials into the pass: it already holds dy
+// and xhat in registers for every element, and a wave's lane covers the SAME
+// column slices on every row it processes — so the partial sums accumulate
+// in registers for free and wb_part's 16-24 MB re-read of dy/x disappears.
+// The block's 4 waves merge through LDS into ONE scratch slab
+// (slab = blockIdx); the grid is capped so nslabs <= MAX_SLABS.
+//
+// NS = 3 adds a third column partial: the sum over rows of the value stored
 // to dx (after the dropout mask and 1/keep scaling), accumulated in fp32
 // from the value AS STORED, i.e. rounded to the output dtype first. When
 // the LayerNorm's input is a linear's output, that sum is the linear's
@@ -328,8 +252,11 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_vec_kernel(
 // differed from those by the accumulated input rounding, up to 0.05 over
 // 256 rows of unit-scale bf16 gradients.) It costs a few VALU ops per
 // element here and saves the linear a pass over its dy. Slab layout is
-// then [3*cols]: dw, db, dxsum.
-template <int DT, bool HAS_RES, bool DROP, int CH, bool XSUM>
+// [NS*cols]: dw, db(, dxsum).
+//
+// NS = 0 (SKY_LN_SPLIT_WB) is the dx pass alone: no accumulators, no LDS
+// merge, and scratch is not touched.
+template <int DT, bool HAS_RES, bool DROP, int CH, int NS>
 __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
     const void* __restrict__ dy, const void* __restrict__ x,
     const void* __restrict__ res, const void* __restrict__ w,
@@ -340,21 +267,19 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const int64_t cols8 = cols / 8;
-  const uint64_t seed =
-      DROP ? rng_seed(salt, state) : 0;
-  const unsigned keep16 = keep_to_16(keep);
-  const float inv_keep = 1.f / keep;
-  constexpr int NV = XSUM ? 3 : 2;
+  const LnDrop drop(DROP, keep, salt, state);
   float xh[CH][8], dxh[CH][8];
-  float sw[CH][8], sb[CH][8], sx[XSUM ? CH : 1][8];
+  float sw[NS ? CH : 1][8], sb[NS ? CH : 1][8], sx[NS == 3 ? CH : 1][8];
+  if constexpr (NS > 0) {
 #pragma unroll
-  for (int c = 0; c < CH; ++c)
+    for (int c = 0; c < CH; ++c)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sw[c][j] = 0.f;
-      sb[c][j] = 0.f;
-      if constexpr (XSUM) sx[c][j] = 0.f;
-    }
+      for (int j = 0; j < 8; ++j) {
+        sw[c][j] = 0.f;
+        sb[c][j] = 0.f;
+        if constexpr (NS == 3) sx[c][j] = 0.f;
+      }
+  }
   unsigned kbits[CH];
   for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows;
        row += (int64_t)gridDim.x * 4) {
@@ -366,26 +291,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
       const int64_t i8 = (int64_t)c * WAVE + lane;
       if (i8 < cols8) {
         float xv[8], dyv[8], wv[8];
-        Vec8<DT>::load(x, base8 + i8, xv);
-        if (DROP) {
-          const uint64_t e8 = (uint64_t)(base8 + i8);
-          const uint64_t z0 = rng_hash(seed, e8 * 2);
-          const uint64_t z1 = rng_hash(seed, e8 * 2 + 1);
-          kbits[c] = 0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const uint64_t zz = j < 4 ? z0 : z1;
-            bool kb = (unsigned)((zz >> (16 * (j & 3))) & 0xFFFFu) < keep16;
-            kbits[c] |= (unsigned)kb << j;
-            xv[j] = kb ? xv[j] * inv_keep : 0.f;
-          }
-        }
-        if (HAS_RES) {
-          float r[8];
-          Vec8<DT>::load(res, base8 + i8, r);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xv[j] += r[j];
-        }
+        LN_LOAD_ROW(x, res, base8 + i8, drop, xv, kbits[c]);
         Vec8<DT>::load(dy, base8 + i8, dyv);
         Vec8<DT>::load(w, i8, wv);
 #pragma unroll
@@ -394,8 +300,10 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
           dxh[c][j] = dyv[j] * wv[j];
           s1 += dxh[c][j];
           s2 += dxh[c][j] * xh[c][j];
-          sw[c][j] += dyv[j] * xh[c][j];
-          sb[c][j] += dyv[j];
+          if constexpr (NS > 0) {
+            sw[c][j] += dyv[j] * xh[c][j];
+            sb[c][j] += dyv[j];
+          }
         }
       }
     }
@@ -413,9 +321,9 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
         if (DROP) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
-            o[j] = ((kbits[c] >> j) & 1u) ? o[j] * inv_keep : 0.f;
+            o[j] = ((kbits[c] >> j) & 1u) ? o[j] * drop.inv_keep : 0.f;
         }
-        if constexpr (XSUM) {
+        if constexpr (NS == 3) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
             sx[c][j] += DT == DT_BF16 ? bf16_to_f32(f32_to_bf16(o[j])) : o[j];
@@ -424,43 +332,43 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
       }
     }
   }
-  // merge the 4 waves' partials through LDS (halves the slab count vs
-  // per-wave slabs -> half the scratch the final stage must re-read),
-  // then ONE slab write per block.
-  __shared__ float mrg[NV][CH * 512];
-  for (int i = threadIdx.x; i < NV * CH * 512; i += 256)
-    (&mrg[0][0])[i] = 0.f;
-  __syncthreads();
-  for (int k = 0; k < 4; ++k) {
-    if (wid == k) {
+  if constexpr (NS > 0) {
+    // merge the 4 waves' partials through LDS (halves the slab count vs
+    // per-wave slabs -> half the scratch the final stage must re-read),
+    // then ONE slab write per block.
+    __shared__ float mrg[NS][CH * 512];
+    for (int i = threadIdx.x; i < NS * CH * 512; i += 256)
+      (&mrg[0][0])[i] = 0.f;
+    __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+      if (wid == k) {
 #pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const int64_t i8 = (int64_t)c * WAVE + lane;
-        if (i8 < cols8) {
+        for (int c = 0; c < CH; ++c) {
+          const int64_t i8 = (int64_t)c * WAVE + lane;
+          if (i8 < cols8) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            mrg[0][i8 * 8 + j] += sw[c][j];
-            mrg[1][i8 * 8 + j] += sb[c][j];
-            if constexpr (XSUM) mrg[NV - 1][i8 * 8 + j] += sx[c][j];
+            for (int j = 0; j < 8; ++j) {
+              mrg[0][i8 * 8 + j] += sw[c][j];
+              mrg[1][i8 * 8 + j] += sb[c][j];
+              if constexpr (NS == 3) mrg[2][i8 * 8 + j] += sx[c][j];
+            }
           }
         }
       }
+      __syncthreads();
     }
-    __syncthreads();
-  }
-  float* base = scratch + (int64_t)blockIdx.x * NV * cols8 * 8;
-  for (int i = threadIdx.x; i < cols8 * 8; i += 256) {
-    base[i] = mrg[0][i];
-    base[cols8 * 8 + i] = mrg[1][i];
-    if constexpr (XSUM) base[2 * cols8 * 8 + i] = mrg[NV - 1][i];
+    float* base = scratch + (int64_t)blockIdx.x * NS * cols8 * 8;
+    for (int i = threadIdx.x; i < cols8 * 8; i += 256) {
+      base[i] = mrg[0][i];
+      base[cols8 * 8 + i] = mrg[1][i];
+      if constexpr (NS == 3) base[2 * cols8 * 8 + i] = mrg[2][i];
+    }
   }
 }
 
 // column-parallel dw/db, two-stage, no atomics, outputs need no zero-init:
 // stage 1 writes per-slab partials to scratch [nslabs][2*cols] fp32
 // (dw partial at [y][c], db partial at [y][cols+c]); stage 2 reduces.
-#define LN_SLABS 1024
-
 template <int DT, bool HAS_RES, bool DROP, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ln_bwd_wb_part_kernel(
     const void* __restrict__ dy, const void* __restrict__ x,
@@ -473,33 +381,14 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_wb_part_kernel(
   const int64_t slab = blockIdx.y;
   const int64_t r0 = slab * rows_per_slab;
   const int64_t r1 = min(rows, r0 + rows_per_slab);
-  const uint64_t seed =
-      DROP ? rng_seed(salt, state) : 0;
-  const unsigned keep16 = keep_to_16(keep);
-  const float inv_keep = 1.f / keep;
+  const LnDrop drop(DROP, keep, salt, state);
   float sw[8] = {0.f}, sb[8] = {0.f};
   for (int64_t r = r0; r < r1; ++r) {
     const float mu = mean[r], rs = rstd[r];
     float xv[8], dyv[8];
-    Vec8<DT>::load(x, r * cols8 + c8, xv);
+    [[maybe_unused]] unsigned kbits;
+    LN_LOAD_ROW(x, res, r * cols8 + c8, drop, xv, kbits);
     Vec8<DT>::load(dy, r * cols8 + c8, dyv);
-    if (DROP) {
-      const uint64_t e8 = (uint64_t)(r * cols8 + c8);
-      const uint64_t z0 = rng_hash(seed, e8 * 2);
-      const uint64_t z1 = rng_hash(seed, e8 * 2 + 1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint64_t zz = j < 4 ? z0 : z1;
-        bool kb = (unsigned)((zz >> (16 * (j & 3))) & 0xFFFFu) < keep16;
-        xv[j] = kb ? xv[j] * inv_keep : 0.f;
-      }
-    }
-    if (HAS_RES) {
-      float rv[8];
-      Vec8<DT>::load(res, r * cols8 + c8, rv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xv[j] += rv[j];
-    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       sw[j] += dyv[j] * (xv[j] - mu) * rs;
@@ -609,64 +498,74 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_dx_kernel(
   }
 }
 
-// widest chunk count the three-sum (XSUM) dx kernel is built for: CH=2 and
-// CH=4 compile without scratch; CH=8 is at the VGPR limit with two sums
-// already and is not offered.
+// widest chunk count the three-sum dx kernel is built for: CH=2 and CH=4
+// compile without scratch; CH=8 is at the VGPR limit with two sums already
+// and is not offered.
 #define LN_XSUM_MAXCH 4
 
-// Fused backward: dx (+dres) and the per-block column partials in one
-// kernel, then the final slab reduction. XSUM also produces dxsum[cols],
-// the column sum of the stored dx.
-template <bool XSUM>
-static int ln_bwd_cs_launch(hipStream_t s, uint64_t dy, uint64_t x,
-                            uint64_t res, uint64_t w, uint64_t mean,
-                            uint64_t rstd, uint64_t dx, uint64_t dw,
-                            uint64_t db, uint64_t dxsum, uint64_t scratch,
-                            int64_t rows, int64_t cols, int dt, float keep,
-                            uint64_t salt, uint64_t state, uint64_t dres) {
-  const bool has_res = res != 0;
-  const bool drop = keep < 1.f;
-  // one slab per BLOCK (LDS-merged): grid 512 keeps the dx streaming fed
-  // (256 starved it: 16.9 vs 9.9 us) while the final re-reads only
-  // 512 slabs (SKY_LN_CS_GRID overrides for sweeps)
-  unsigned gmax = 512;
-  if (const char* e = getenv("SKY_LN_CS_GRID")) gmax = (unsigned)atoi(e);
-  if (gmax > LN_SLABS) gmax = LN_SLABS;
-  if (gmax < 1) gmax = 1;
-  unsigned grid = (unsigned)((rows + 3) / 4);
+// what every backward launch below needs of the entry points' arguments
+struct LnBwdArgs {
+  hipStream_t s;
+  uint64_t dy, x, res, w, mean, rstd, dx, dres, scratch;
+  int64_t rows, cols;
+  int dt;
+  float keep;
+  uint64_t salt, state;
+};
+
+// The vectorized dx kernel with NS column sums; returns its grid, which for
+// NS > 0 is the number of slabs it wrote ([NS*cols] fp32 each).
+template <int NS>
+static int64_t ln_bwd_dx_launch(const LnBwdArgs& a) {
+  unsigned gmax = 8192;
+  if (NS > 0) {
+    // one slab per BLOCK (LDS-merged): grid 512 keeps the dx streaming fed
+    // (256 starved it: 16.9 vs 9.9 us) while the final re-reads only
+    // 512 slabs (SKY_LN_CS_GRID overrides for sweeps)
+    gmax = 512;
+    if (const char* e = getenv("SKY_LN_CS_GRID")) gmax = (unsigned)atoi(e);
+    if (gmax > (unsigned)MAX_SLABS) gmax = MAX_SLABS;
+    if (gmax < 1) gmax = 1;
+  }
+  unsigned grid = (unsigned)((a.rows + 3) / 4);
   if (grid > gmax) grid = gmax;
-  const int ch = (int)((cols / 8 + WAVE - 1) / WAVE);
-#define LNCS(DT, HR, DR, CH)                                                   \
-  hipLaunchKernelGGL((ln_bwd_dx_cs_kernel<DT, HR, DR, CH, XSUM>), dim3(grid),  \
-                     dim3(256), 0, s, (const void*)dy, (const void*)x,         \
-                     (const void*)res, (const void*)w, (const float*)mean,     \
-                     (const float*)rstd, (void*)dx, (void*)dres,               \
-                     (float*)scratch, rows, cols, keep, salt,                  \
-                     (const unsigned long long*)state)
-#define LNCS_CH(DT, HR, DR)                                                    \
-  do {                                                                         \
-    if (ch <= 2) LNCS(DT, HR, DR, 2);                                          \
-    else if (ch <= 4) LNCS(DT, HR, DR, 4);                                     \
-    else if constexpr (!XSUM) LNCS(DT, HR, DR, 8);                             \
-  } while (0)
-#define LNCS_D(DT, HR)                                                         \
-  do { if (drop) LNCS_CH(DT, HR, true); else LNCS_CH(DT, HR, false); } while (0)
-  if (dt == DT_F32) { if (has_res) LNCS_D(DT_F32, true); else LNCS_D(DT_F32, false); }
-  else              { if (has_res) LNCS_D(DT_BF16, true); else LNCS_D(DT_BF16, false); }
-#undef LNCS_D
-#undef LNCS_CH
-#undef LNCS
-  const int64_t nslabs = (int64_t)grid;  // one slab per block
-  constexpr int NV = XSUM ? 3 : 2;
-  dim3 g2((unsigned)((cols + 15) / 16));
-  if (dt == DT_BF16)
-    hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16, NV>), g2,
-                       dim3(1024), 0, s, (const float*)scratch, (void*)dw,
-                       (void*)db, (void*)dxsum, cols, nslabs);
-  else
-    hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32, NV>), g2,
-                       dim3(1024), 0, s, (const float*)scratch, (void*)dw,
-                       (void*)db, (void*)dxsum, cols, nslabs);
+  dispatch_tags<NS == 3 ? LN_XSUM_MAXCH : LN_MAXCH>(
+      a.dt, a.res != 0, a.keep < 1.f, ln_chunks(a.cols),
+      [&](auto DT, auto HR, auto DR, auto CH) {
+        hipLaunchKernelGGL((ln_bwd_dx_cs_kernel<DT, HR, DR, CH, NS>),
+                           dim3(grid), dim3(256), 0, a.s, (const void*)a.dy,
+                           (const void*)a.x, (const void*)a.res,
+                           (const void*)a.w, (const float*)a.mean,
+                           (const float*)a.rstd, (void*)a.dx, (void*)a.dres,
+                           (float*)a.scratch, a.rows, a.cols, a.keep, a.salt,
+                           (const unsigned long long*)a.state);
+      });
+  return (int64_t)grid;
+}
+
+// The final slab reduction: dw, db (and dxsum for NV = 3) from nslabs slabs
+// of [NV*cols] fp32, written in the param dtype.
+template <int NV>
+static void ln_bwd_wb_final_launch(const LnBwdArgs& a, uint64_t dw,
+                                   uint64_t db, uint64_t dxsum,
+                                   int64_t nslabs) {
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.cols + 15) / 16)), dim3(1024),
+                       0, a.s, (const float*)a.scratch, (void*)dw, (void*)db,
+                       (void*)dxsum, a.cols, nslabs);
+  };
+  if (a.dt == DT_BF16) launch(ln_bwd_wb_final_kernel<256, DT_BF16, NV>);
+  else launch(ln_bwd_wb_final_kernel<256, DT_F32, NV>);
+}
+
+// Fused backward: dx (+dres) and the per-block column partials in one
+// kernel, then the final slab reduction. NS = 3 also produces dxsum[cols],
+// the column sum of the stored dx.
+template <int NS>
+static int ln_bwd_cs_launch(const LnBwdArgs& a, uint64_t dw, uint64_t db,
+                            uint64_t dxsum) {
+  const int64_t nslabs = ln_bwd_dx_launch<NS>(a);  // one slab per block
+  ln_bwd_wb_final_launch<NS>(a, dw, db, dxsum, nslabs);
   LAUNCH_CHECK();
   return 0;
 }
@@ -678,52 +577,28 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
                                  int64_t cols, int dt, float keep,
                                  uint64_t salt, uint64_t state,
                                  uint64_t dres) {
-  hipStream_t s = (hipStream_t)stream;
+  const LnBwdArgs a{(hipStream_t)stream, dy, x, res, w, mean, rstd, dx, dres,
+                    scratch, rows, cols, dt, keep, salt, state};
+  hipStream_t s = a.s;
   bool has_res = res != 0;
   bool drop = keep < 1.f;
   if (drop && !ln_fast_ok(cols)) return (int)hipErrorInvalidValue;
-  // fused path: the dx kernel also produces the dw/db per-wave column
-  // partials (kills wb_part's re-read of dy/x); SKY_LN_SPLIT_WB=1 restores
-  // the separate 3-kernel chain for A/B.
+  // fused path: the dx kernel also produces the dw/db column partials
+  // (kills wb_part's re-read of dy/x); SKY_LN_SPLIT_WB=1 restores the
+  // separate 3-kernel chain for A/B.
   const bool fused_wb =
       ln_fast_ok(cols) && scratch != 0 && !getenv("SKY_LN_SPLIT_WB");
-  if (fused_wb)
-    return ln_bwd_cs_launch<false>(s, dy, x, res, w, mean, rstd, dx, dw, db, 0,
-                                   scratch, rows, cols, dt, keep, salt, state,
-                                   dres);
+  if (fused_wb) return ln_bwd_cs_launch<2>(a, dw, db, 0);
   if (ln_fast_ok(cols)) {
-    unsigned grid = (unsigned)((rows + 3) / 4);
-    if (grid > 8192u) grid = 8192u;
-    const int ch = (int)((cols / 8 + WAVE - 1) / WAVE);
-#define LNBV(DT, HR, DR, CH)                                                   \
-  hipLaunchKernelGGL((ln_bwd_dx_vec_kernel<DT, HR, DR, CH>), dim3(grid),       \
-                     dim3(256), 0, s, (const void*)dy, (const void*)x,         \
-                     (const void*)res, (const void*)w, (const float*)mean,     \
-                     (const float*)rstd, (void*)dx, (void*)dres, rows, cols,   \
-                     keep, salt, (const unsigned long long*)state)
-#define LNBV_CH(DT, HR, DR)                                                    \
-  do {                                                                         \
-    if (ch <= 2) LNBV(DT, HR, DR, 2);                                          \
-    else if (ch <= 4) LNBV(DT, HR, DR, 4);                                     \
-    else LNBV(DT, HR, DR, 8);                                                  \
-  } while (0)
-#define LNBV_D(DT, HR)                                                         \
-  do { if (drop) LNBV_CH(DT, HR, true); else LNBV_CH(DT, HR, false); } while (0)
-    if (dt == DT_F32) { if (has_res) LNBV_D(DT_F32, true); else LNBV_D(DT_F32, false); }
-    else              { if (has_res) LNBV_D(DT_BF16, true); else LNBV_D(DT_BF16, false); }
-#undef LNBV_D
-#undef LNBV_CH
-#undef LNBV
+    ln_bwd_dx_launch<0>(a);
   } else {
     dim3 grid((unsigned)(rows < 4096 ? rows : 4096));
-#define LNBD(DT, HR)                                                           \
-  hipLaunchKernelGGL((ln_bwd_dx_kernel<DT, 256, HR>), grid, dim3(256), 0, s,   \
-                     (const void*)dy, (const void*)x, (const void*)res,        \
-                     (const void*)w, (const float*)mean, (const float*)rstd,   \
-                     (void*)dx, rows, cols)
-    if (dt == DT_F32) { if (has_res) LNBD(DT_F32, true); else LNBD(DT_F32, false); }
-    else              { if (has_res) LNBD(DT_BF16, true); else LNBD(DT_BF16, false); }
-#undef LNBD
+    dispatch_tags(dt, has_res, false, 0, [&](auto DT, auto HR, auto, auto) {
+      hipLaunchKernelGGL((ln_bwd_dx_kernel<DT, 256, HR>), grid, dim3(256), 0,
+                         s, (const void*)dy, (const void*)x, (const void*)res,
+                         (const void*)w, (const float*)mean,
+                         (const float*)rstd, (void*)dx, rows, cols);
+    });
   }
   if (cols % 8 == 0 && scratch != 0) {
     constexpr int BLOCK = 128;
@@ -733,31 +608,18 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     const int64_t gx = (cols8 + BLOCK - 1) / BLOCK;
     int64_t nslabs = 1024 / gx;
     if (nslabs < 128) nslabs = 128;
-    if (nslabs > LN_SLABS) nslabs = LN_SLABS;
+    if (nslabs > MAX_SLABS) nslabs = MAX_SLABS;
     if (nslabs > rows) nslabs = rows;
     const int64_t slab = (rows + nslabs - 1) / nslabs;
     dim3 grid((unsigned)gx, (unsigned)nslabs);
-#define LNWBP(DT, HR, DR)                                                      \
-  hipLaunchKernelGGL((ln_bwd_wb_part_kernel<DT, HR, DR, BLOCK>), grid,         \
-                     dim3(BLOCK), 0, s, (const void*)dy, (const void*)x,       \
-                     (const void*)res, (const float*)mean,                     \
-                     (const float*)rstd, (float*)scratch, rows, cols8, slab,   \
-                     keep, salt, (const unsigned long long*)state)
-#define LNWBP_D(DT, HR)                                                        \
-  do { if (drop) LNWBP(DT, HR, true); else LNWBP(DT, HR, false); } while (0)
-    if (dt == DT_F32) { if (has_res) LNWBP_D(DT_F32, true); else LNWBP_D(DT_F32, false); }
-    else              { if (has_res) LNWBP_D(DT_BF16, true); else LNWBP_D(DT_BF16, false); }
-#undef LNWBP_D
-#undef LNWBP
-    dim3 g2((unsigned)((cols + 15) / 16));
-    if (dt == DT_BF16)
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_BF16, 2>), g2,
-                         dim3(1024), 0, s, (const float*)scratch, (void*)dw,
-                         (void*)db, (void*)nullptr, cols, nslabs);
-    else
-      hipLaunchKernelGGL((ln_bwd_wb_final_kernel<256, DT_F32, 2>), g2,
-                         dim3(1024), 0, s, (const float*)scratch, (void*)dw,
-                         (void*)db, (void*)nullptr, cols, nslabs);
+    dispatch_tags(dt, has_res, drop, 0, [&](auto DT, auto HR, auto DR, auto) {
+      hipLaunchKernelGGL((ln_bwd_wb_part_kernel<DT, HR, DR, BLOCK>), grid,
+                         dim3(BLOCK), 0, s, (const void*)dy, (const void*)x,
+                         (const void*)res, (const float*)mean,
+                         (const float*)rstd, (float*)scratch, rows, cols8,
+                         slab, keep, salt, (const unsigned long long*)state);
+    });
+    ln_bwd_wb_final_launch<2>(a, dw, db, 0, nslabs);
   } else {
     constexpr int BLOCK = 256;
     // slab sized so the grid fills 256 CUs (cols/256 col-blocks * row-slabs)
@@ -766,14 +628,13 @@ SKY_EXPORT int sky_layernorm_bwd(uint64_t stream, uint64_t dy, uint64_t x,
       slab *= 2;
     dim3 grid((unsigned)((cols + BLOCK - 1) / BLOCK),
               (unsigned)((rows + slab - 1) / slab));
-#define LNWB(DT, HR)                                                           \
-  hipLaunchKernelGGL((ln_bwd_wb_kernel<DT, HR, BLOCK>), grid, dim3(BLOCK), 0,  \
-                     s, (const void*)dy, (const void*)x, (const void*)res,     \
-                     (const float*)mean, (const float*)rstd, (float*)dw,       \
-                     (float*)db, rows, cols, slab)
-    if (dt == DT_F32) { if (has_res) LNWB(DT_F32, true); else LNWB(DT_F32, false); }
-    else              { if (has_res) LNWB(DT_BF16, true); else LNWB(DT_BF16, false); }
-#undef LNWB
+    dispatch_tags(dt, has_res, false, 0, [&](auto DT, auto HR, auto, auto) {
+      hipLaunchKernelGGL((ln_bwd_wb_kernel<DT, HR, BLOCK>), grid, dim3(BLOCK),
+                         0, s, (const void*)dy, (const void*)x,
+                         (const void*)res, (const float*)mean,
+                         (const float*)rstd, (float*)dw, (float*)db, rows,
+                         cols, slab);
+    });
   }
   LAUNCH_CHECK();
   return 0;
@@ -787,7 +648,7 @@ SKY_EXPORT int sky_layernorm_bwd_xsum_ok(int64_t cols) {
 // sky_layernorm_bwd plus dxsum[cols] = column sum of the stored dx (param
 // dtype, like dw/db): the bias gradient of a linear feeding this LayerNorm.
 // Always the fused dx + column-partials path; needs scratch of
-// [LN_SLABS][3*cols] fp32. Unsupported widths return an error so the
+// [MAX_SLABS][3*cols] fp32. Unsupported widths return an error so the
 // caller composes the two ops instead.
 SKY_EXPORT int sky_layernorm_bwd_xsum(uint64_t stream, uint64_t dy, uint64_t x,
                                       uint64_t res, uint64_t w, uint64_t mean,
@@ -798,7 +659,7 @@ SKY_EXPORT int sky_layernorm_bwd_xsum(uint64_t stream, uint64_t dy, uint64_t x,
                                       uint64_t dres, uint64_t dxsum) {
   if (!sky_layernorm_bwd_xsum_ok(cols) || scratch == 0 || dxsum == 0)
     return (int)hipErrorInvalidValue;
-  return ln_bwd_cs_launch<true>((hipStream_t)stream, dy, x, res, w, mean, rstd,
-                                dx, dw, db, dxsum, scratch, rows, cols, dt,
-                                keep, salt, state, dres);
+  const LnBwdArgs a{(hipStream_t)stream, dy, x, res, w, mean, rstd, dx, dres,
+                    scratch, rows, cols, dt, keep, salt, state};
+  return ln_bwd_cs_launch<3>(a, dw, db, dxsum);
 }

@@ -66,7 +66,12 @@ allocator_config = dict(
 train_config = dict(
     max_epoch=1,
     max_iter=30,
-    optimizer=dict(lr=1e-3, momentum=0.0, weight_decay=0.0),
+    optimizer=dict(lr=1e-3, momentum=0.0, weight_decay=0.0),  # type="SGD"
+    # the BERT fine-tuning form: AdamW, clip folded into the update kernel,
+    # no decay on biases and LayerNorm parameters
+    # optimizer=dict(type="AdamW", lr=2e-5, betas=(0.9, 0.999), eps=1e-8,
+    #                weight_decay=0.01, max_grad_norm=1.0, no_decay="1d"),
+    # grad_clip_norm=1.0,  # Runner's eager per-rank clip (for SGD)
     num_microbatches=int(os.environ.get("SKY_MICROBATCHES", 0)),  # 0 = auto
     schedule=os.environ.get("SKY_SCHEDULE", "gpipe"),  # gpipe | 1f1b | sequential
     log_interval=1,

@@ -63,7 +63,7 @@ def main():
         Allocator, DeviceBenchmarker, ModelBenchmarker, WorkerManager,
     )
     from skycomputing_amd.logger import Logger
-    from skycomputing_amd.optim import FusedSGD
+    from skycomputing_amd.optim import build_optimizer
     from skycomputing_amd.parallel import PartitionPlan, PipelineEngine, init_distributed
     from skycomputing_amd.runner import Runner
     from skycomputing_amd.stimulator import Stimulator
@@ -165,13 +165,8 @@ def main():
         )
 
     tcfg = cfg.train_config
-    opt_cfg = tcfg.get("optimizer", {})
-    opt = FusedSGD(
-        engine.parameters(),
-        lr=opt_cfg.get("lr", 1e-3),
-        momentum=opt_cfg.get("momentum", 0.0),
-        weight_decay=opt_cfg.get("weight_decay", 0.0),
-    )
+    # type="SGD" (default) | "AdamW"; the other keys are the constructor's
+    opt = build_optimizer(tcfg.get("optimizer", {}), engine.parameters())
 
     M = tcfg.get("num_microbatches", 0) or (1 if world == 1 else min(8, cfg.data_config["batch_size"]))
     runner = Runner(
@@ -182,6 +177,9 @@ def main():
         schedule=tcfg.get("schedule", "gpipe"),
         logger=logger,
         log_interval=tcfg.get("log_interval", 1),
+        # the Runner's own eager clip; leave it unset with
+        # optimizer=dict(type="AdamW", max_grad_norm=...), which clips in-kernel
+        grad_clip_norm=tcfg.get("grad_clip_norm"),
     )
     for hook_cfg in tcfg.get("hooks", []):
         runner.register_hook(build_hook(dict(hook_cfg)))

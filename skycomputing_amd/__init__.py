@@ -7,7 +7,7 @@ A from-scratch rebuild of the capabilities of hpcaitech/SkyComputing
     TensorPipe RPC;
   * hand-written HIP/CDNA4 kernels for the BERT hot path (fully-fused
     MFMA attention fwd+bwd, fused LayerNorm(+residual+dropout), bias-GELU,
-    masked softmax, fused embedding, multi-tensor SGD, MFMA GEMM with
+    masked softmax, fused embedding, multi-tensor SGD and AdamW, MFMA GEMM with
     fused epilogues) instead of eager CUDA ops + optional apex;
   * benchmark-driven even/dynamic/optimal layer allocation with an EXACT
     subset-DP solver replacing the reference's 300s/20%-gap MIP;
@@ -20,12 +20,12 @@ __version__ = "0.2.0"
 
 from . import builder, config, dataset, dynamics, models, ops, parallel, registry, runner
 from .logger import Logger
-from .optim import FusedSGD
+from .optim import FusedAdamW, FusedSGD, build_optimizer
 from .stimulator import Stimulator
 from .timer import DeviceTimer, DistributedTimer
 
 __all__ = [
     "builder", "config", "dataset", "dynamics", "models", "ops", "parallel",
-    "registry", "runner", "Logger", "FusedSGD", "Stimulator", "DeviceTimer",
-    "DistributedTimer", "__version__",
+    "registry", "runner", "Logger", "FusedSGD", "FusedAdamW", "build_optimizer",
+    "Stimulator", "DeviceTimer", "DistributedTimer", "__version__",
 ]

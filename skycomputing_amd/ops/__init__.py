@@ -25,7 +25,7 @@ __all__ = [
     "layer_norm", "bias_gelu", "bias_tanh", "masked_softmax", "dropout",
     "attention_context", "attention_block", "linear_act",
     "linear_residual_layer_norm",
-    "embedding_fused", "sgd_step",
+    "embedding_fused", "sgd_step", "adamw_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
 ]
 
@@ -295,3 +295,13 @@ def sgd_step(params, grads, lr, momentum=0.0, weight_decay=0.0,
              momentum_bufs=None, master_params=None):
     """Multi-tensor SGD step; fused HIP path lives in optim.FusedSGD."""
     eager.sgd_step(params, grads, lr, momentum, weight_decay, momentum_bufs, master_params)
+
+
+def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9,
+               beta2=0.999, eps=1e-8, weight_decay=0.01, master_params=None,
+               max_grad_norm=None, no_decay=None):
+    """Multi-tensor AdamW step with the clip folded in; fused HIP path
+    lives in optim.FusedAdamW."""
+    return eager.adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr,
+                            beta1, beta2, eps, weight_decay, master_params,
+                            max_grad_norm, no_decay)

@@ -158,3 +158,56 @@ def sgd_step(
             target.copy_((target.float().add_(gf, alpha=-lr)).to(target.dtype))
         if master_params is not None:
             p.copy_(target.to(p.dtype))
+
+
+@torch.no_grad()
+def adamw_step(
+    params: list[torch.Tensor],
+    grads: list[torch.Tensor],
+    exp_avgs: list[torch.Tensor],
+    exp_avg_sqs: list[torch.Tensor],
+    step: int,
+    lr: float,
+    beta1: float = 0.9,
+    beta2: float = 0.999,
+    eps: float = 1e-8,
+    weight_decay: float = 0.01,
+    master_params: list[torch.Tensor] | None = None,
+    max_grad_norm: float | None = None,
+    no_decay: list[bool] | None = None,
+):
+    """Multi-tensor AdamW (decoupled decay, eps outside the square root) in
+    fp32 torch ops; ``step`` is this step's number, counted from 1.
+
+    With ``max_grad_norm`` the gradients are read through the factor
+    ``min(1, max_grad_norm / (norm + 1e-6))`` of
+    ``torch.nn.utils.clip_grad_norm_`` without being rewritten. Tensors
+    flagged in ``no_decay`` get no weight decay. ``exp_avgs`` and
+    ``exp_avg_sqs`` are fp32; with ``master_params`` (fp32) the update is
+    applied to the master and the param is refreshed from it. Returns
+    ``(norm, clip)`` as 0-dim fp32 tensors, or ``(None, None)`` without
+    clipping."""
+    live = [i for i, g in enumerate(grads) if g is not None]
+    norm = clip = None
+    if max_grad_norm is not None and live:
+        sq = torch.stack([grads[i].float().square().sum() for i in live]).sum()
+        norm = sq.sqrt()
+        clip = (max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
+    step_size = lr / (1.0 - beta1 ** step)
+    rsqrt_bc2 = 1.0 / math.sqrt(1.0 - beta2 ** step)
+    for i in live:
+        p = params[i]
+        target = master_params[i] if master_params is not None else p
+        m, v = exp_avgs[i], exp_avg_sqs[i]
+        g = grads[i].float()
+        if clip is not None:
+            g = g * clip
+        wd = 0.0 if (no_decay is not None and no_decay[i]) else weight_decay
+        t32 = target.float().mul(1.0 - lr * wd)
+        m.mul_(beta1).add_(g, alpha=1.0 - beta1)
+        v.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
+        t32.addcdiv_(m, v.sqrt().mul_(rsqrt_bc2).add_(eps), value=-step_size)
+        target.copy_(t32.to(target.dtype))
+        if master_params is not None:
+            p.copy_(target.to(p.dtype))
+    return norm, clip

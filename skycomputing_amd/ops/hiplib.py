@@ -52,6 +52,11 @@ def _register_signatures(lib):
         # strm dy ids tids pids wemb temb pemb lnw mean rstd dwe dte dpe dlnw dlnb | rows cols dt
         "sky_sgd_step": [u64, u64, i64, f32, f32, f32, i32, i32],
         #                strm descs n   lr   mom  wd   dt   flags
+        "sky_adamw_tick": [u64, u64, f64, f64],  # strm hyper beta1 beta2
+        "sky_gradnorm_partials": [u64, u64, i64, u64, i32],  # strm descs n partials dt
+        "sky_gradnorm_finish": [u64, u64, i64, u64, f32],  # strm partials n hyper max_norm
+        "sky_adamw_step": [u64, u64, i64, u64, f64, f64, f32, f32, i32, i32],
+        #                  strm descs n   hyper b1   b2   eps  wd   dt   flags
         "sky_detect_mem": [u64, u64],  # free_out, total_out (host ptrs)
         "sky_dropout_fwd": [u64, u64, u64, i64, f32, u64, u64, i32],
         #                   strm  x    y    n   keep salt state dt

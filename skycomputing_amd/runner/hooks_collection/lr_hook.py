@@ -1,10 +1,17 @@
 """Learning-rate schedule hook (warmup + decay).
 
-Sets ``runner.optimizer.lr`` before every iteration; FusedSGD reads the
-attribute at each eager step. NOTE: the captured-step executors
-(GraphedTrainStep / GraphedPipelineStep) freeze the lr INSIDE the graph at
-capture time — schedules only act on the eager Runner path, which is where
-hooks run. The reference has no scheduler at all (constant lr=1e-3).
+Sets ``runner.optimizer.lr`` before every iteration. Whether a schedule
+reaches a GRAPHED step depends on where the optimizer keeps its lr:
+
+* FusedAdamW keeps lr on the device (its hyper block); the setter is a
+  stream-ordered write, so a captured step replayed after ``opt.lr = x``
+  uses x.
+* FusedSGD reads the attribute at each eager step and passes it as a launch
+  argument: the captured-step executors (GraphedTrainStep /
+  GraphedPipelineStep) freeze it INSIDE the graph at capture time, and
+  schedules only act on the eager Runner path.
+
+The reference has no scheduler at all (constant lr=1e-3).
 """
 
 from __future__ import annotations

@@ -26,6 +26,8 @@ Dataflow tuples between pipeline stages:
 
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -240,6 +242,27 @@ class BertLayerBody(nn.Module):
     def forward(self, attn_out, ext_mask):
         inter = self.intermediate(attn_out)
         return attn_out, inter, ext_mask
+
+    def fuse_with_next(self, nxt):
+        """SequentialWrapper's pairing protocol: followed by its Tail on the
+        same stage, the two run as one op (ops.ffn_block; on GPU a single
+        autograd node) that returns what nxt(*self(...)) returns. None
+        keeps them separate: another successor, SKY_NO_FFN_BLOCK=1, or the
+        two in different train/eval modes."""
+        if (not isinstance(nxt, BertLayerTail)
+                or os.environ.get("SKY_NO_FFN_BLOCK") == "1"
+                or self.training != nxt.training):
+            return None
+
+        def body_and_tail(attn_out, ext_mask):
+            up, ln = self.intermediate, nxt.layer_norm
+            hidden = ops.ffn_block(
+                attn_out, up.weight, up.bias, nxt.dense.weight, nxt.dense.bias,
+                ln.weight, ln.bias, ln.eps, nxt.dropout_p, nxt.training,
+                up.act)
+            return hidden, ext_mask
+
+        return body_and_tail
 
     def layer_flops(self, batch: int, seq: int) -> float:
         return 2.0 * batch * seq * self.config.hidden_size * self.config.intermediate_size

@@ -23,7 +23,7 @@ from .eager import ACT_FNS, gelu, swish  # re-export
 
 __all__ = [
     "layer_norm", "bias_gelu", "bias_tanh", "masked_softmax", "dropout",
-    "attention_context", "attention_block", "linear_act",
+    "attention_context", "attention_block", "ffn_block", "linear_act",
     "linear_residual_layer_norm",
     "embedding_fused", "sgd_step", "adamw_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
@@ -244,6 +244,27 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
         hidden_dropout_p, training)
 
 
+def _linear_gelu_node_ok(x, weight) -> bool:
+    """Whether ops.linear_act runs gelu(linear(x)) as LinearGeluFn (one GEMM
+    with the bias + gelu + pre-activation epilogue) for a GPU x with bias."""
+    from .functions import _g2_enabled, _g2_fit, _use_hblt
+
+    # GELU_AUX_BIAS epilogue: this hipBLASLt build only supports it for
+    # fp32 D (bf16 returns HIPBLAS_STATUS_NOT_SUPPORTED — probed on HW,
+    # tools/hblt_probe.py), so the fused linear+gelu is fp32-only and
+    # opt-in; the bf16 hot path keeps GEMM + the HIP bias+gelu kernel.
+    if (_use_hblt() and os.environ.get("SKY_HBLT_GELU") == "1"
+            and x.dtype == torch.float32 and weight.shape[0] % 8 == 0):
+        return True
+    # v2 hand-GEMM path: one 256^2 8-phase kernel with the bias+gelu
+    # epilogue fused (and the pre-activation stored for backward)
+    if x.dtype == torch.bfloat16:
+        rows = x.numel() // x.shape[-1]
+        return (_g2_enabled("fwd", rows, weight.shape[0], weight.shape[1])
+                and _g2_fit(rows, weight.shape[0], weight.shape[1]))
+    return False
+
+
 def linear_act(x, weight, bias, act: str = "gelu"):
     """Linear + bias + activation (the reference's LinearActivation).
 
@@ -251,27 +272,49 @@ def linear_act(x, weight, bias, act: str = "gelu"):
     pre-activation save fused into the GEMM); SKY_NO_HBLT=1 falls back to
     GEMM + the standalone HIP bias+gelu kernel."""
     if _use_hip(x) and act == "gelu" and bias is not None:
-        from .functions import LinearGeluFn, _use_hblt
+        if _linear_gelu_node_ok(x, weight):
+            from .functions import LinearGeluFn
 
-        # GELU_AUX_BIAS epilogue: this hipBLASLt build only supports it for
-        # fp32 D (bf16 returns HIPBLAS_STATUS_NOT_SUPPORTED — probed on HW,
-        # tools/hblt_probe.py), so the fused linear+gelu is fp32-only and
-        # opt-in; the bf16 hot path keeps GEMM + the HIP bias+gelu kernel.
-        if (_use_hblt() and os.environ.get("SKY_HBLT_GELU") == "1"
-                and x.dtype == torch.float32 and weight.shape[0] % 8 == 0):
             return LinearGeluFn.apply(x, weight, bias)
-        # v2 hand-GEMM path: one 256^2 8-phase kernel with the bias+gelu
-        # epilogue fused (and the pre-activation stored for backward)
-        if x.dtype == torch.bfloat16:
-            from .functions import _g2_enabled, _g2_fit
-
-            rows = x.numel() // x.shape[-1]
-            if (_g2_enabled("fwd", rows, weight.shape[0], weight.shape[1])
-                    and _g2_fit(rows, weight.shape[0], weight.shape[1])):
-                return LinearGeluFn.apply(x, weight, bias)
         y = torch.nn.functional.linear(x, weight)
         return bias_gelu(y, bias)
     return eager.linear_act(x, weight, bias, act)
+
+
+def ffn_block(x, up_weight, up_bias, down_weight, down_bias, ln_weight,
+              ln_bias, eps: float = 1e-12, hidden_dropout_p: float = 0.0,
+              training: bool = False, act: str = "gelu"):
+    """The FFN two-thirds of an encoder block:
+    LN(dropout(act(x @ Wup^T + bup) @ Wdown^T + bdown) + x)
+    for x [..., H].
+
+    Where ops.linear_act would run its one-GEMM gelu node AND
+    ops.linear_residual_layer_norm its node — GPU, gelu, both biases
+    present, a shape the fused ffn-up forward takes, the LayerNorm width
+    supported by the three-sum backward: one autograd node (FfnBlockFn)
+    whose backward sums x's two gradients inside the ffn-up dgrad GEMM and
+    finishes its four column sums in one launch. Everything else — CPU,
+    other activations, dtypes and shapes, SKY_NO_FFN_BLOCK=1,
+    SKY_NO_LN_DBIAS=1 — is the composition of ops.linear_act and
+    ops.linear_residual_layer_norm."""
+    if (
+        act == "gelu" and up_bias is not None and down_bias is not None
+        and x.dtype in (torch.float32, torch.bfloat16) and _use_hip(x)
+    ):
+        from .functions import (
+            FfnBlockFn, ffn_block_enabled, ln_dbias_enabled, ln_xsum_width_ok,
+        )
+
+        if (ffn_block_enabled() and ln_dbias_enabled()
+                and ln_xsum_width_ok(down_weight.shape[0])
+                and _linear_gelu_node_ok(x, up_weight)):
+            p = hidden_dropout_p if training else 0.0
+            return FfnBlockFn.apply(x, up_weight, up_bias, down_weight,
+                                    down_bias, ln_weight, ln_bias, eps, p)
+    inter = linear_act(x, up_weight, up_bias, act)
+    return linear_residual_layer_norm(
+        inter, down_weight, down_bias, ln_weight, ln_bias, eps, x,
+        hidden_dropout_p, training)
 
 
 def embedding_fused(

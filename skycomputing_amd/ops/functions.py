@@ -8,6 +8,7 @@ fp32 (tests/test_ops_gpu.py).
 
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -41,6 +42,52 @@ def _red_scratch(cols: int, pairs: int, device) -> torch.Tensor:
     """fp32 scratch for the two-stage column reductions:
     [_CS_SLABS slabs][pairs*cols]."""
     return torch.empty(_CS_SLABS * pairs * cols, dtype=torch.float32, device=device)
+
+
+def merged_finish_enabled() -> bool:
+    """SKY_NO_MERGED_FINISH=1 keeps every producer's own final reduction
+    launch in the block nodes (A/B)."""
+    return os.environ.get("SKY_NO_MERGED_FINISH") != "1"
+
+
+class PendingFinish:
+    """The slab reductions a backward has left pending: producers run
+    through their sky_*_parts entry points with slot() as the job argument,
+    then ONE sky_colsum_finish launch writes all their outputs, in the
+    order the producers ran. The jobs live in host memory and travel to the
+    kernel by value, so nothing is allocated or copied under graph capture.
+    Holds the producers' scratch tensors until the finish is enqueued."""
+
+    def __init__(self):
+        self._jobs = (hiplib.FinishJob * hiplib.FINISH_MAX_JOBS)()
+        self.n = 0
+        self._keep = []
+
+    def slot(self) -> int:
+        """Address of the next free job, to hand to a *_parts entry point."""
+        if self.n >= hiplib.FINISH_MAX_JOBS:
+            raise RuntimeError("too many pending finish jobs")
+        self._jobs[self.n].nv = 0
+        return ctypes.addressof(self._jobs[self.n])
+
+    def took(self, *scratch) -> bool:
+        """After a *_parts call: keep the job if the producer left one.
+        False means the producer finished its outputs itself."""
+        if self._jobs[self.n].nv == 0:
+            return False
+        self._keep.extend(scratch)
+        self.n += 1
+        return True
+
+    def run(self):
+        if self.n:
+            check(
+                hiplib.require().sky_colsum_finish(
+                    _stream(), ctypes.addressof(self._jobs), self.n),
+                "sky_colsum_finish",
+            )
+        self.n = 0
+        self._keep.clear()
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -748,12 +795,15 @@ def _ln_fwd(h, residual, ln_w, ln_b, eps, keep):
     return y, mean, rstd, salt
 
 
-def _ln_bwd(dy, h, residual, ln_w, mean, rstd, keep, salt, xsum):
+def _ln_bwd(dy, h, residual, ln_w, mean, rstd, keep, salt, xsum,
+            pending=None):
     """sky_layernorm_bwd (or, with xsum, sky_layernorm_bwd_xsum) for
     cols % 8 == 0, where the final reduction stage writes the param dtype
     directly. Returns (dh, d_ln_w, d_ln_b, dxsum, dres) with dxsum the
     column sum of dh as stored (None without xsum) and dres the residual's
-    gradient (dh itself without dropout, None without a residual)."""
+    gradient (dh itself without dropout, None without a residual). With a
+    PendingFinish the final reduction is left to pending.run(): d_ln_w,
+    d_ln_b and dxsum hold nothing until then."""
     lib = hiplib.require()
     cols = h.shape[-1]
     rows = h.numel() // cols
@@ -768,7 +818,11 @@ def _ln_bwd(dy, h, residual, ln_w, mean, rstd, keep, salt, xsum):
     args = (_stream(), ptr(dy), ptr(h), ptr(residual), ptr(ln_w), ptr(mean),
             ptr(rstd), ptr(dh), ptr(d_ln_w), ptr(d_ln_b), ptr(scratch), rows,
             cols, _dt(h), keep, salt, state_ptr, ptr(dres))
-    if xsum:
+    if pending is not None:
+        check(lib.sky_layernorm_bwd_parts(*args, ptr(dxsum), pending.slot()),
+              "sky_layernorm_bwd_parts")
+        pending.took(scratch)
+    elif xsum:
         check(lib.sky_layernorm_bwd_xsum(*args, ptr(dxsum)),
               "sky_layernorm_bwd_xsum")
     else:
@@ -872,9 +926,12 @@ class AttentionBlockFn(torch.autograd.Function):
          rstd) = ctx.saved_tensors
         B, S, _, nh, d = qkv.shape
         H = nh * d
+        # the LN and dbqkv slab reductions finish in one launch, after the
+        # attention backward (SKY_NO_MERGED_FINISH=1: one launch each)
+        pending = PendingFinish() if merged_finish_enabled() else None
         dh, d_ln_w, d_ln_b, dbo, dres = _ln_bwd(
             dy.contiguous(), h, x2, ln_w, mean, rstd, ctx.keep, ctx.salt,
-            xsum=True)
+            xsum=True, pending=pending)
         dh2 = dh.view(-1, H)
         dctx = _dgrad(dh2, wo)
         dwo = _wgrad_plain(dh2, c2, wo)
@@ -885,15 +942,17 @@ class AttentionBlockFn(torch.autograd.Function):
         # the kernels write every element, so no memset
         slabs = torch.empty(B * ((S + 63) // 64) * 3 * H, dtype=torch.float32,
                             device=qkv.device)
-        check(
-            lib.sky_attn_bwd_dbias(
-                _stream(), ptr(qkv), ptr(dctx), ptr(mask), ptr(m), ptr(lsum),
+        args = (_stream(), ptr(qkv), ptr(dctx), ptr(mask), ptr(m), ptr(lsum),
                 ptr(pdT), ptr(dsT), ptr(dqkv), B, S, nh, d, ctx.scale,
                 ctx.akeep, ctx.asalt, rng_state().data_ptr(), ptr(slabs),
-                ptr(dbqkv), _dt(dbqkv),
-            ),
-            "sky_attn_bwd_dbias",
-        )
+                ptr(dbqkv), _dt(dbqkv))
+        if pending is not None:
+            check(lib.sky_attn_bwd_dbias_parts(*args, pending.slot()),
+                  "sky_attn_bwd_dbias_parts")
+            pending.took(slabs)
+            pending.run()
+        else:
+            check(lib.sky_attn_bwd_dbias(*args), "sky_attn_bwd_dbias")
         dqkv2 = dqkv.view(-1, 3 * H)
         dwqkv = _wgrad_plain(dqkv2, x2, wqkv)
         # d hidden = dres + dqkv @ Wqkv, accumulated by the GEMM. Without
@@ -911,6 +970,48 @@ class AttentionBlockFn(torch.autograd.Function):
                 d_ln_w, d_ln_b, None, None)
 
 
+def _linear_gelu_fwd(x2, weight, bias):
+    """gelu(x2 @ weight.T + bias) on contiguous 2D x2 in ONE GEMM that also
+    stores the pre-activation: the v2 hand GEMM where its fwd site is
+    enabled for the shape, else the hipBLASLt GELU_AUX_BIAS epilogue.
+    Returns (y, aux)."""
+    M, K = x2.shape
+    N = weight.shape[0]
+    g2 = gemm2_fwd(x2, weight, bias, gelu=True, want_z=True)
+    if g2 is not None:
+        return g2
+    y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+    aux = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+    check(
+        hiplib.require().sky_hblt_linear_gelu_aux(
+            _stream(), ptr(x2), ptr(weight), ptr(bias), ptr(y), ptr(aux),
+            M, N, K, _dt(x2), _dt(aux)
+        ),
+        "sky_hblt_linear_gelu_aux",
+    )
+    return y, aux
+
+
+def _gelu_bwd(dy2, aux, weight, pending=None):
+    """sky_bias_gelu_bwd with aux as the pre-activation: returns
+    (dpre, dbias). With a PendingFinish, dbias's slab reduction is left to
+    pending.run() where the kernel's streaming path applies."""
+    lib = hiplib.require()
+    rows, N = dy2.shape
+    dpre = torch.empty_like(dy2)
+    db = torch.empty(N, dtype=weight.dtype, device=weight.device)
+    scratch = _red_scratch(N, 1, dy2.device)
+    args = (_stream(), ptr(dy2), ptr(aux), 0, ptr(dpre), ptr(db),
+            ptr(scratch), rows, N, _dt(dy2))
+    if pending is not None:
+        check(lib.sky_bias_gelu_bwd_parts(*args, pending.slot()),
+              "sky_bias_gelu_bwd_parts")
+        pending.took(scratch)
+    else:
+        check(lib.sky_bias_gelu_bwd(*args), "sky_bias_gelu_bwd")
+    return dpre, db
+
+
 class LinearGeluFn(torch.autograd.Function):
     """Fused linear + bias + GELU via the hipBLASLt GELU_AUX_BIAS epilogue
     (the reference's LinearActivation, scaelum/model/bert_layers.py:60-108):
@@ -924,50 +1025,89 @@ class LinearGeluFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         xs = x.shape
         x2 = x.reshape(-1, xs[-1]).contiguous()
-        M, K = x2.shape
-        N = weight.shape[0]
-        g2 = gemm2_fwd(x2, weight, bias, gelu=True, want_z=True)
-        if g2 is not None:
-            y, aux = g2
-        else:
-            lib = hiplib.require()
-            y = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
-            aux = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
-            check(
-                lib.sky_hblt_linear_gelu_aux(
-                    _stream(), ptr(x2), ptr(weight), ptr(bias), ptr(y), ptr(aux),
-                    M, N, K, _dt(x2), _dt(aux)
-                ),
-                "sky_hblt_linear_gelu_aux",
-            )
+        y, aux = _linear_gelu_fwd(x2, weight, bias)
         ctx.save_for_backward(x2, weight, aux)
         ctx.xshape = xs
-        return y.view(*xs[:-1], N)
+        return y.view(*xs[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        lib = hiplib.require()
         x2, weight, aux = ctx.saved_tensors
-        N = weight.shape[0]
-        dy2 = dy.reshape(-1, N)
+        dy2 = dy.reshape(-1, weight.shape[0])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
-        rows = dy2.shape[0]
-        dpre = torch.empty_like(dy2)
-        db = torch.empty(N, dtype=weight.dtype, device=weight.device)
-        scratch = _red_scratch(N, 1, dy2.device)
-        check(
-            lib.sky_bias_gelu_bwd(
-                _stream(), ptr(dy2), ptr(aux), 0, ptr(dpre), ptr(db),
-                ptr(scratch), rows, N, _dt(dy2)
-            ),
-            "sky_bias_gelu_bwd",
-        )
+        dpre, db = _gelu_bwd(dy2, aux, weight)
         dx = _dgrad(dpre, weight).view(ctx.xshape)
         dw = gemm2_wgrad(dpre, x2)
         if dw is None:
             dw = dpre.t().mm(x2)
         return dx, dw, db
+
+
+def ffn_block_enabled() -> bool:
+    """SKY_NO_FFN_BLOCK=1 keeps the FFN two-thirds of an encoder block as
+    its two autograd nodes (A/B)."""
+    return os.environ.get("SKY_NO_FFN_BLOCK") != "1"
+
+
+class FfnBlockFn(torch.autograd.Function):
+    """The FFN two-thirds of an encoder block as ONE autograd node:
+
+        LN(dropout(gelu(x @ Wup^T + bup) @ Wdown^T + bdown) + x)
+
+    Forward kernels, saved tensors and the single dropout-salt draw are
+    those of LinearGeluFn followed by LinearResidualLayerNormFn, so y is
+    bit-identical to that composition. One node lets the backward
+      * fold autograd's add of x's two gradients (residual branch and
+        ffn-up linear) into the ffn-up dgrad GEMM (beta = 1 on dres), and
+      * finish its four column sums (d_ln_w, d_ln_b, dbdown from the LN
+        backward, dbup from the gelu backward) in one launch.
+    Domain: where ops.linear_act takes LinearGeluFn and
+    ops.linear_residual_layer_norm takes its node (ops.ffn_block)."""
+
+    @staticmethod
+    def forward(ctx, x, wup, bup, wdown, bdown, ln_w, ln_b, eps, dropout_p):
+        xs = x.shape
+        H = xs[-1]
+        x2 = x.reshape(-1, H).contiguous()
+        inter, aux = _linear_gelu_fwd(x2, wup, bup)
+        h = _linear_fwd(inter, wdown, bdown)
+        keep = 1.0 - dropout_p
+        y, mean, rstd, salt = _ln_fwd(h, x2, ln_w, ln_b, eps, keep)
+        ctx.save_for_backward(x2, wup, aux, inter, wdown, h, ln_w, mean, rstd)
+        ctx.keep, ctx.salt = keep, salt
+        ctx.xshape = xs
+        return y.view(xs)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x2, wup, aux, inter, wdown, h, ln_w, mean,
+         rstd) = ctx.saved_tensors
+        H = x2.shape[-1]
+        pending = PendingFinish() if merged_finish_enabled() else None
+        dh, d_ln_w, d_ln_b, dbdown, dres = _ln_bwd(
+            dy.contiguous().view(-1, H), h, x2, ln_w, mean, rstd, ctx.keep,
+            ctx.salt, xsum=True, pending=pending)
+        d_inter = _dgrad(dh, wdown)
+        dwdown = _wgrad_plain(dh, inter, wdown)
+        dpre, dbup = _gelu_bwd(d_inter, aux, wup, pending)
+        if pending is not None:
+            pending.run()
+        dwup = gemm2_wgrad(dpre, x2)
+        if dwup is None:
+            dwup = dpre.t().mm(x2)
+        # d x = dres + dpre @ Wup, accumulated by the GEMM. Without dropout
+        # dres IS dh; its readers above are already enqueued on this
+        # stream, so updating it in place is safe.
+        g2 = gemm2_dgrad(dpre, wup)
+        if g2 is not None:
+            dres.add_(g2)
+        else:
+            dres.addmm_(dpre, wup)
+        if dbdown.dtype != wdown.dtype:
+            dbdown = dbdown.to(wdown.dtype)
+        return (dres.view(ctx.xshape), dwup, dbup, dwdown, dbdown, d_ln_w,
+                d_ln_b, None, None)
 
 
 class EmbeddingFusedFn(torch.autograd.Function):

@@ -587,6 +587,31 @@ SKY_EXPORT int sky_attn_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
 // qkv, taken from the kernels' registers instead of a re-read of dqkv.
 // scratch: fp32 [B * ceil(S/64)][3*h*64], no memset needed; dbias_dt is
 // the DT_* tag of the dbias buffer.
+// job == nullptr: the slab reduction runs here; otherwise it is left
+// pending in *job.
+static int attn_bwd_dbias_impl(uint64_t stream, uint64_t qkv, uint64_t dout,
+                               uint64_t mask, uint64_t m, uint64_t lsum,
+                               uint64_t pdT, uint64_t dsT, uint64_t dqkv,
+                               int64_t B, int64_t S, int64_t h, int64_t d,
+                               float scale, float keep, uint64_t salt,
+                               uint64_t state, uint64_t scratch,
+                               uint64_t dbias, int dbias_dt,
+                               SkyFinishJob* job) {
+  if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  launch_attn_bwd_pair<true>(s, qkv, dout, mask, m, lsum, pdT, dsT, dqkv, B, S,
+                             h, scale, keep, salt, state, (float*)scratch);
+  const int64_t cols = 3 * h * ATT_D, nslabs = B * ((S + 63) / 64);
+  if (job)
+    sky_finish_job_set(job, scratch, dbias, 0, 0, nslabs, cols, 1, dbias_dt);
+  else
+    sky_launch_colsum_final(s, (const float*)scratch, (void*)dbias, cols,
+                            nslabs, dbias_dt);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 SKY_EXPORT int sky_attn_bwd_dbias(uint64_t stream, uint64_t qkv, uint64_t dout,
                                   uint64_t mask, uint64_t m, uint64_t lsum,
                                   uint64_t pdT, uint64_t dsT, uint64_t dqkv,
@@ -594,13 +619,23 @@ SKY_EXPORT int sky_attn_bwd_dbias(uint64_t stream, uint64_t qkv, uint64_t dout,
                                   float scale, float keep, uint64_t salt,
                                   uint64_t state, uint64_t scratch,
                                   uint64_t dbias, int dbias_dt) {
-  if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
-    return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  launch_attn_bwd_pair<true>(s, qkv, dout, mask, m, lsum, pdT, dsT, dqkv, B, S,
-                             h, scale, keep, salt, state, (float*)scratch);
-  sky_launch_colsum_final(s, (const float*)scratch, (void*)dbias,
-                          3 * h * ATT_D, B * ((S + 63) / 64), dbias_dt);
-  LAUNCH_CHECK();
-  return 0;
+  return attn_bwd_dbias_impl(stream, qkv, dout, mask, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, nullptr);
+}
+
+// sky_attn_bwd_dbias without its final: dqkv and the column-partial scratch
+// are written, dbias's slab reduction is described in *job (a host
+// SkyFinishJob) for sky_colsum_finish.
+SKY_EXPORT int sky_attn_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t mask, uint64_t m,
+    uint64_t lsum, uint64_t pdT, uint64_t dsT, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt,
+    uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_bwd_dbias_impl(stream, qkv, dout, mask, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, (SkyFinishJob*)job);
 }

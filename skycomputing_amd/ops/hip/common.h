@@ -208,6 +208,30 @@ DEV float gelu_grad_f(float x) {
 void sky_launch_colsum_final(hipStream_t s, const float* scratch, void* out,
                              int64_t cols, int64_t nslabs, int dtout);
 
+// A slab reduction whose producer has run but whose final has not: scratch
+// holds nslabs slabs of [nv][cols] fp32, and out[v][c] = sum over the slabs
+// of scratch[(slab*nv + v)*cols + c], written as dtout (a DT_* tag). The
+// *_parts entry points fill one of these instead of launching their final
+// (nv = 0: nothing pending, the producer finished its own outputs);
+// sky_colsum_finish runs up to SKY_FINISH_MAX_JOBS of them in one launch.
+// Mirrored by ops/hiplib.py: FinishJob.
+struct SkyFinishJob {
+  uint64_t scratch;
+  uint64_t out[3];
+  int64_t nslabs;
+  int64_t cols;
+  int32_t nv;
+  int32_t dtout;
+};
+constexpr int SKY_FINISH_MAX_JOBS = 4;
+
+static inline void sky_finish_job_set(SkyFinishJob* job, uint64_t scratch,
+                                      uint64_t o0, uint64_t o1, uint64_t o2,
+                                      int64_t nslabs, int64_t cols, int nv,
+                                      int dtout) {
+  *job = SkyFinishJob{scratch, {o0, o1, o2}, nslabs, cols, nv, dtout};
+}
+
 // Most slabs any two-stage column reduction writes: callers size the fp32
 // scratch for MAX_SLABS slabs (ops/functions.py: _CS_SLABS).
 constexpr int MAX_SLABS = 1024;

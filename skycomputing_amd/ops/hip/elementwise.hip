@@ -233,6 +233,109 @@ void sky_launch_colsum_final(hipStream_t s, const float* scratch, void* out,
                        s, scratch, out, cols, nslabs);
 }
 
+// Several slab reductions in ONE launch: up to SKY_FINISH_MAX_JOBS jobs, each
+// what colsum_final_kernel (nv = 1) or ln_bwd_wb_final_kernel (nv = 2, 3)
+// does for one producer: scratch [nslabs][nv][cols] fp32 -> nv outputs of
+// cols elements. The jobs travel by value as kernel arguments; block0 is
+// each job's first block, so a block finds its job from its index and the
+// branch on the job is block-uniform. Per column the arithmetic is that of
+// the separate finals (same group bounds, same order in the group, same
+// tree), so every output has the same bits.
+struct FinishJobs {
+  SkyFinishJob j[SKY_FINISH_MAX_JOBS];
+  unsigned block0[SKY_FINISH_MAX_JOBS];
+  int n;
+};
+
+template <int NV, int DTOUT>
+DEV void finish_job_block(const SkyFinishJob& jb, unsigned block,
+                          float (*lds)[64][17]) {
+  const float* __restrict__ scratch = (const float*)jb.scratch;
+  const int64_t cols = jb.cols, nslabs = jb.nslabs;
+  const int c = threadIdx.x & 15;
+  const int g = threadIdx.x >> 4;  // 0..63
+  const int64_t col = (int64_t)block * 16 + c;
+  const int64_t per = (nslabs + 63) / 64;
+  float s[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = 0.f;
+  if (col < cols) {
+    const int64_t y1 = min(nslabs, (int64_t)(g + 1) * per);
+    for (int64_t y = (int64_t)g * per; y < y1; ++y) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) s[v] += scratch[(y * NV + v) * cols + col];
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < NV; ++v) lds[v][g][c] = s[v];
+  __syncthreads();
+  for (int st = 32; st >= 1; st >>= 1) {
+    if (g < st) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) lds[v][g][c] += lds[v][g + st][c];
+    }
+    __syncthreads();
+  }
+  if (g == 0 && col < cols) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      store_elem<DTOUT>((void*)jb.out[v], col, lds[v][0][c]);
+  }
+}
+
+__global__ __launch_bounds__(1024) void colsum_finish_jobs_kernel(
+    const FinishJobs jobs) {
+  __shared__ float lds[3][64][17];
+  int ji = 0;
+#pragma unroll
+  for (int k = 1; k < SKY_FINISH_MAX_JOBS; ++k)
+    if (k < jobs.n && blockIdx.x >= jobs.block0[k]) ji = k;
+  const SkyFinishJob& jb = jobs.j[ji];
+  const unsigned block = blockIdx.x - jobs.block0[ji];
+  const bool bf = jb.dtout == DT_BF16;
+  switch (jb.nv) {
+    case 1:
+      if (bf) finish_job_block<1, DT_BF16>(jb, block, lds);
+      else finish_job_block<1, DT_F32>(jb, block, lds);
+      break;
+    case 2:
+      if (bf) finish_job_block<2, DT_BF16>(jb, block, lds);
+      else finish_job_block<2, DT_F32>(jb, block, lds);
+      break;
+    default:
+      if (bf) finish_job_block<3, DT_BF16>(jb, block, lds);
+      else finish_job_block<3, DT_F32>(jb, block, lds);
+      break;
+  }
+}
+
+// Runs the pending jobs jobs[0..n) (host array, as the *_parts entry points
+// filled them) in one launch, in the order given. n = 0 launches nothing.
+SKY_EXPORT int sky_colsum_finish(uint64_t stream, uint64_t jobs, int n) {
+  if (n < 0 || n > SKY_FINISH_MAX_JOBS || (n > 0 && jobs == 0))
+    return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const SkyFinishJob* src = (const SkyFinishJob*)jobs;
+  FinishJobs fj{};
+  unsigned nblocks = 0;
+  for (int k = 0; k < n; ++k) {
+    const SkyFinishJob& jb = src[k];
+    if (jb.nv < 1 || jb.nv > 3 || jb.cols < 1 || jb.nslabs < 1 ||
+        jb.scratch == 0 || (jb.dtout != DT_F32 && jb.dtout != DT_BF16))
+      return (int)hipErrorInvalidValue;
+    for (int v = 0; v < jb.nv; ++v)
+      if (jb.out[v] == 0) return (int)hipErrorInvalidValue;
+    fj.j[k] = jb;
+    fj.block0[k] = nblocks;
+    nblocks += (unsigned)((jb.cols + 15) / 16);
+  }
+  fj.n = n;
+  hipLaunchKernelGGL(colsum_finish_jobs_kernel, dim3(nblocks), dim3(1024), 0,
+                     (hipStream_t)stream, fj);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 template <int DT, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void colsum_kernel(
     const void* __restrict__ src, float* __restrict__ out, int64_t rows,
@@ -294,13 +397,17 @@ SKY_EXPORT int sky_colsum(uint64_t stream, uint64_t src, uint64_t out,
   return 0;
 }
 
-SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
-                                 uint64_t b, uint64_t dx, uint64_t db,
-                                 uint64_t scratch, int64_t rows, int64_t cols,
-                                 int dt) {
+// job == nullptr: every path ends with its own final. Otherwise the
+// streaming cs path leaves its final pending in *job; the other paths still
+// finish db themselves and report nothing pending (nv = 0).
+static int bias_gelu_bwd_impl(uint64_t stream, uint64_t dy, uint64_t x,
+                              uint64_t b, uint64_t dx, uint64_t db,
+                              uint64_t scratch, int64_t rows, int64_t cols,
+                              int dt, SkyFinishJob* job) {
   hipStream_t s = (hipStream_t)stream;
   int64_t n = rows * cols;
   const bool hb = b != 0;
+  if (job) job->nv = 0;
   // The fused one-pass variant measures FASTER standalone but SLOWER
   // in-app (+4.9 us/layer vs the dx + two-stage-colsum chain at the bench
   // shape — profiles r01_bench160 diff); the proven chain is the default
@@ -326,7 +433,10 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     dispatch_tags(dt, hb, false, 0, [&](auto DT, auto HB, auto, auto) {
       launch_cs(bias_gelu_bwd_cs_kernel<DT, HB>);
     });
-    sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
+    if (job)
+      sky_finish_job_set(job, scratch, db, 0, 0, nslabs, cols, 1, dt);
+    else
+      sky_launch_colsum_final(s, (const float*)scratch, (void*)db, cols, nslabs, dt);
     LAUNCH_CHECK();
     return 0;
   }
@@ -385,6 +495,28 @@ SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
     launch_colsum<DT_BF16>(s, (const void*)dx, (void*)db, (float*)scratch, rows, cols, dt);
   LAUNCH_CHECK();
   return 0;
+}
+
+SKY_EXPORT int sky_bias_gelu_bwd(uint64_t stream, uint64_t dy, uint64_t x,
+                                 uint64_t b, uint64_t dx, uint64_t db,
+                                 uint64_t scratch, int64_t rows, int64_t cols,
+                                 int dt) {
+  return bias_gelu_bwd_impl(stream, dy, x, b, dx, db, scratch, rows, cols, dt,
+                            nullptr);
+}
+
+// sky_bias_gelu_bwd without the final of its streaming path: dx is written,
+// db's slab reduction is described in *job (a host SkyFinishJob) for
+// sky_colsum_finish. Off that path (cols % 2048 != 0, the SKY_GELU_*
+// switches) db is finished here and job->nv is 0.
+SKY_EXPORT int sky_bias_gelu_bwd_parts(uint64_t stream, uint64_t dy,
+                                       uint64_t x, uint64_t b, uint64_t dx,
+                                       uint64_t db, uint64_t scratch,
+                                       int64_t rows, int64_t cols, int dt,
+                                       uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  return bias_gelu_bwd_impl(stream, dy, x, b, dx, db, scratch, rows, cols, dt,
+                            (SkyFinishJob*)job);
 }
 
 // ---------------- dropout ----------------

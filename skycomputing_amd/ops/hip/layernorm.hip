@@ -561,11 +561,16 @@ static void ln_bwd_wb_final_launch(const LnBwdArgs& a, uint64_t dw,
 // Fused backward: dx (+dres) and the per-block column partials in one
 // kernel, then the final slab reduction. NS = 3 also produces dxsum[cols],
 // the column sum of the stored dx.
+// With a job, the final is left pending in *job for sky_colsum_finish.
 template <int NS>
 static int ln_bwd_cs_launch(const LnBwdArgs& a, uint64_t dw, uint64_t db,
-                            uint64_t dxsum) {
+                            uint64_t dxsum, SkyFinishJob* job = nullptr) {
   const int64_t nslabs = ln_bwd_dx_launch<NS>(a);  // one slab per block
-  ln_bwd_wb_final_launch<NS>(a, dw, db, dxsum, nslabs);
+  if (job)
+    sky_finish_job_set(job, a.scratch, dw, db, dxsum, nslabs, a.cols, NS,
+                       a.dt);
+  else
+    ln_bwd_wb_final_launch<NS>(a, dw, db, dxsum, nslabs);
   LAUNCH_CHECK();
   return 0;
 }
@@ -662,4 +667,36 @@ SKY_EXPORT int sky_layernorm_bwd_xsum(uint64_t stream, uint64_t dy, uint64_t x,
   const LnBwdArgs a{(hipStream_t)stream, dy, x, res, w, mean, rstd, dx, dres,
                     scratch, rows, cols, dt, keep, salt, state};
   return ln_bwd_cs_launch<3>(a, dw, db, dxsum);
+}
+
+// sky_layernorm_bwd (dxsum == 0) or sky_layernorm_bwd_xsum (dxsum != 0)
+// without the final of the fused dx + column-partials path: dx (and dres)
+// are written, and the slab reduction that yields dw, db (and dxsum) is
+// described in *job (a host SkyFinishJob) for sky_colsum_finish. Where the
+// two-sum call is not on that path (width, no scratch, SKY_LN_SPLIT_WB) it
+// runs sky_layernorm_bwd whole and job->nv is 0; the three-sum call refuses
+// what sky_layernorm_bwd_xsum refuses.
+SKY_EXPORT int sky_layernorm_bwd_parts(uint64_t stream, uint64_t dy,
+                                       uint64_t x, uint64_t res, uint64_t w,
+                                       uint64_t mean, uint64_t rstd,
+                                       uint64_t dx, uint64_t dw, uint64_t db,
+                                       uint64_t scratch, int64_t rows,
+                                       int64_t cols, int dt, float keep,
+                                       uint64_t salt, uint64_t state,
+                                       uint64_t dres, uint64_t dxsum,
+                                       uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  SkyFinishJob* jb = (SkyFinishJob*)job;
+  jb->nv = 0;
+  const LnBwdArgs a{(hipStream_t)stream, dy, x, res, w, mean, rstd, dx, dres,
+                    scratch, rows, cols, dt, keep, salt, state};
+  if (dxsum != 0) {
+    if (!sky_layernorm_bwd_xsum_ok(cols) || scratch == 0)
+      return (int)hipErrorInvalidValue;
+    return ln_bwd_cs_launch<3>(a, dw, db, dxsum, jb);
+  }
+  if (ln_fast_ok(cols) && scratch != 0 && !getenv("SKY_LN_SPLIT_WB"))
+    return ln_bwd_cs_launch<2>(a, dw, db, 0, jb);
+  return sky_layernorm_bwd(stream, dy, x, res, w, mean, rstd, dx, dw, db,
+                           scratch, rows, cols, dt, keep, salt, state, dres);
 }

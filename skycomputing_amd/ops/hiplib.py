@@ -21,11 +21,24 @@ _TRIED = False
 # every kernel entry point returns int (0 = ok, nonzero = hipError_t)
 _SIGNATURES: dict[str, list] = {}
 
+FINISH_MAX_JOBS = 4  # SKY_FINISH_MAX_JOBS in ops/hip/common.h
+
 u64 = ctypes.c_uint64
 i64 = ctypes.c_int64
 i32 = ctypes.c_int32
 f32 = ctypes.c_float
 f64 = ctypes.c_double
+
+
+class FinishJob(ctypes.Structure):
+    """SkyFinishJob (ops/hip/common.h): a slab reduction whose producer has
+    run and whose final is pending. Filled by the sky_*_parts entry points
+    (nv == 0: nothing pending), consumed by sky_colsum_finish."""
+
+    _fields_ = [
+        ("scratch", u64), ("out", u64 * 3), ("nslabs", i64), ("cols", i64),
+        ("nv", i32), ("dtout", i32),
+    ]
 
 
 def _register_signatures(lib):
@@ -85,6 +98,15 @@ def _register_signatures(lib):
         "sky_attn_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
         # sky_attn_bwd's arguments + scratch (fp32 [B*ceil(S/64)][3*h*d]),
         # dbias [3*h*d] (column sum of dqkv as stored), dbias dt
+        "sky_attn_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        # sky_attn_bwd_dbias's arguments + job (host FinishJob*): the dbias
+        # slab reduction is left pending there
+        "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
+        # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
+        # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending
+        "sky_bias_gelu_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, u64],
+        # sky_bias_gelu_bwd's arguments + job; job.nv == 0 off the cs path
+        "sky_colsum_finish": [u64, u64, i32],  # strm jobs (host FinishJob[n]) n
         "sky_attn_bwd_fused": [u64] * 7 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout mask m l dqkv | B S h d scale keep salt state
         # (ONE kernel: dQ/dK/dV, P+dS never leave LDS)

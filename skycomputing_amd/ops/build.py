@@ -13,6 +13,7 @@ import glob
 import hashlib
 import json
 import os
+import shlex
 import subprocess
 import sys
 
@@ -26,6 +27,9 @@ CFLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
     "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
 ]
+# extra compile flags for check builds, e.g. SKY_HIPCC_FLAGS=-DSKY_GELU_IEEE_MATH
+# (ops/hip/common.h); part of the stamp, so changing them rebuilds
+CFLAGS += shlex.split(os.environ.get("SKY_HIPCC_FLAGS", ""))
 
 
 def _source_hash(sources: list[str]) -> str:

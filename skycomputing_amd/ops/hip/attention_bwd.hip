@@ -140,6 +140,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd1s_kernel(
       if (kt >= NT) continue;
       const int col = kt * 16 + lm;
       ushort4_t ds4, pd4;
+      float dsf[4], pdf[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = qtok_base + lg * 4 + r;
@@ -152,11 +153,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd1s_kernel(
           dp = kbit ? dp * inv_keep : 0.f;
         }
         const float ds = scale * p * (dp - dot[r]);
+        dsf[r] = ds;
+        pdf[r] = pd;
+      }
+      ds4 = f32x4_to_bf16x4(dsf[0], dsf[1], dsf[2], dsf[3]);
+      pd4 = f32x4_to_bf16x4(pdf[0], pdf[1], pdf[2], pdf[3]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
         const int rl = lg * 4 + r;
         *(ushort_t*)lds_at(lds, swz(32768 + w * 4096 + rl * 256 + col * 2, rl, 15)) =
-            f32_to_bf16(ds);
-        ds4[r] = f32_to_bf16(ds);
-        pd4[r] = f32_to_bf16(pd);
+            ds4[r];
       }
       if (col < S) {
         const size_t o = ((size_t)bh * S + col) * S + qtok_base + lg * 4;

@@ -159,10 +159,14 @@ DEV void att_store_rows16(ushort_t* __restrict__ dst, int rstride,
                           int lg) {
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
+    // a lane's rows r and r + 1 share one packed convert
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < 4; r += 2) {
       const int row = row0 + lg * 4 + r;
-      if (row < S) dst[(size_t)row * rstride + ct * 16 + lm] = f32_to_bf16(acc[ct][r]);
+      const unsigned int v2 = f32x2_to_bf16x2(acc[ct][r], acc[ct][r + 1]);
+      if (row < S) dst[(size_t)row * rstride + ct * 16 + lm] = (ushort_t)v2;
+      if (row + 1 < S)
+        dst[(size_t)(row + 1) * rstride + ct * 16 + lm] = (ushort_t)(v2 >> 16);
     }
   }
 }
@@ -176,12 +180,18 @@ DEV void att_store_rows16x2(ushort_t* __restrict__ d0,
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < 4; r += 2) {
       const int row = row0 + lg * 4 + r;
       const int c = ct * 16 + lm;
+      const unsigned int v0 = f32x2_to_bf16x2(a0[ct][r], a0[ct][r + 1]);
+      const unsigned int v1 = f32x2_to_bf16x2(a1[ct][r], a1[ct][r + 1]);
       if (row < S) {
-        d0[(size_t)row * rstride + c] = f32_to_bf16(a0[ct][r]);
-        d1[(size_t)row * rstride + c] = f32_to_bf16(a1[ct][r]);
+        d0[(size_t)row * rstride + c] = (ushort_t)v0;
+        d1[(size_t)row * rstride + c] = (ushort_t)v1;
+      }
+      if (row + 1 < S) {
+        d0[(size_t)(row + 1) * rstride + c] = (ushort_t)(v0 >> 16);
+        d1[(size_t)(row + 1) * rstride + c] = (ushort_t)(v1 >> 16);
       }
     }
   }

@@ -28,13 +28,32 @@ DEV float bf16_to_f32(ushort_t u) {
   return v.f;
 }
 
+// fp32 -> bf16, round-to-nearest-even, by the hardware convert
+// (v_cvt_pk_bf16_f32). For every non-NaN input the bits are those of the
+// integer formula ((i + 0x7fff + ((i >> 16) & 1)) >> 16) these kernels used
+// before; a NaN stays a NaN, where the formula carried some payloads over
+// into +-0 or +-Inf (tests/test_bf16_round_gpu.py walks all 2^32 inputs).
+typedef __attribute__((ext_vector_type(2))) float float2_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
+typedef __attribute__((ext_vector_type(4))) unsigned int uint4_t;
+
 DEV ushort_t f32_to_bf16(float f) {
-  union { unsigned int i; float f; } v;
-  v.f = f;
-  // round-to-nearest-even
-  unsigned int lsb = (v.i >> 16) & 1u;
-  v.i += 0x7fffu + lsb;
-  return (ushort_t)(v.i >> 16);
+  return __builtin_bit_cast(ushort_t, (__bf16)f);
+}
+
+// Two neighbouring values in one instruction: lo in bits 0..15, hi in
+// bits 16..31, i.e. the little-endian image of {bf16(lo), bf16(hi)}.
+DEV unsigned int f32x2_to_bf16x2(float lo, float hi) {
+  const float2_t v = {lo, hi};
+  return __builtin_bit_cast(unsigned int,
+                            __builtin_convertvector(v, bf16x2_t));
+}
+
+// Four values as a ushort4 (the 8-byte P/dS packs of the attention kernels)
+DEV ushort4_t f32x4_to_bf16x4(float a, float b, float c, float d) {
+  const uint2_t v = {f32x2_to_bf16x2(a, b), f32x2_to_bf16x2(c, d)};
+  return __builtin_bit_cast(ushort4_t, v);
 }
 
 // dtype tags matching hiplib._DT
@@ -51,10 +70,10 @@ template <> struct Vec8<DT_BF16> {
     for (int j = 0; j < 8; ++j) f[j] = bf16_to_f32(v[j]);
   }
   static DEV void store(void* p, int64_t i8, const float f[8]) {
-    ushort8_t v;
+    uint4_t v;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(f[j]);
-    ((ushort8_t*)p)[i8] = v;
+    for (int j = 0; j < 4; ++j) v[j] = f32x2_to_bf16x2(f[2 * j], f[2 * j + 1]);
+    ((uint4_t*)p)[i8] = v;
   }
 };
 template <> struct Vec8<DT_F32> {
@@ -184,21 +203,44 @@ DEV unsigned keep_to_16(float keep) {
 // Branch-free erf (Abramowitz & Stegun 7.1.26, |err| <= 1.5e-7 absolute —
 // far below bf16 resolution): ~12 VALU ops vs OCML erff's ~30 with range
 // branches. Feeds the exact (erf) GELU, not the tanh approximation.
-DEV float erf_fast(float x) {
+//
+// The reciprocal is one v_rcp_f32 (1 ulp) where an IEEE divide is about 11
+// instructions; gelu_grad_f evaluates exp(-x^2/2) once and hands it to the
+// erf as well as the pdf ((x/sqrt 2)^2 and x^2/2 differ by the rounding of
+// k only). -DSKY_GELU_IEEE_MATH restores the divide and the two
+// exponentials, i.e. the earlier bits: it exists to check the rest of a
+// change for identity against an older build, not for users.
+
+// erf(x) given e = exp(-x*x)
+DEV float erf_fast_e(float x, float e) {
   const float ax = fabsf(x);
+#ifdef SKY_GELU_IEEE_MATH
   const float t = 1.f / fmaf(0.3275911f, ax, 1.f);
+#else
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
+#endif
   const float p = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f),
                                            1.421413741f), -0.284496736f),
                            0.254829592f);
-  const float r = 1.f - p * __expf(-ax * ax);
+  const float r = 1.f - p * e;
   return copysignf(r, x);
+}
+DEV float erf_fast(float x) {
+  const float ax = fabsf(x);
+  return erf_fast_e(x, __expf(-ax * ax));
 }
 DEV float gelu_f(float x) { return 0.5f * x * (1.f + erf_fast(x * 0.70710678118654752f)); }
 DEV float gelu_grad_f(float x) {
   const float k = 0.70710678118654752f;       // 1/sqrt(2)
   const float c = 0.3989422804014327f;        // 1/sqrt(2*pi)
+#ifdef SKY_GELU_IEEE_MATH
   float cdf = 0.5f * (1.f + erf_fast(x * k));
   float pdf = c * __expf(-0.5f * x * x);
+#else
+  const float e = __expf(-0.5f * x * x);
+  float cdf = 0.5f * (1.f + erf_fast_e(x * k, e));
+  float pdf = c * e;
+#endif
   return cdf + x * pdf;
 }
 

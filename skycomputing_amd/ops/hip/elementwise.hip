@@ -155,16 +155,36 @@ __global__ __launch_bounds__(256) void bias_gelu_bwd_cs_kernel(
   float bv[8];
   if (HAS_B) Vec8<DT>::load(b, c8, bv);
   float s[8] = {0.f};
-  for (int64_t r = r0; r < r1; ++r) {
-    float v[8], d[8];
-    Vec8<DT>::load(x, r * cols8 + c8, v);
-    Vec8<DT>::load(dy, r * cols8 + c8, d);
+  // one row's math and store; rows reach s[] in ascending order
+  auto row = [&](int64_t r, const float (&v)[8], float (&d)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       d[j] *= gelu_grad_f(HAS_B ? v[j] + bv[j] : v[j]);
       s[j] += d[j];
     }
     Vec8<DT>::store(dx, r * cols8 + c8, d);
+  };
+  // Two rows per trip: all four 16-byte loads are issued before any math,
+  // so a wave has twice the bytes in flight, and the compiler interleaves
+  // the two rows' math behind a single wait. It does not carry row r + 1's
+  // loads across row r's math (each trip still starts by waiting for its
+  // own loads); the other waves of the SIMD cover that. A last odd row goes
+  // alone.
+  int64_t r = r0;
+  for (; r + 1 < r1; r += 2) {
+    float va[8], da[8], vb[8], db[8];
+    Vec8<DT>::load(x, r * cols8 + c8, va);
+    Vec8<DT>::load(dy, r * cols8 + c8, da);
+    Vec8<DT>::load(x, (r + 1) * cols8 + c8, vb);
+    Vec8<DT>::load(dy, (r + 1) * cols8 + c8, db);
+    row(r, va, da);
+    row(r + 1, vb, db);
+  }
+  if (r < r1) {
+    float v[8], d[8];
+    Vec8<DT>::load(x, r * cols8 + c8, v);
+    Vec8<DT>::load(dy, r * cols8 + c8, d);
+    row(r, v, d);
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) scratch[(slab * cols8 + c8) * 8 + j] = s[j];

@@ -349,16 +349,25 @@ __global__ __launch_bounds__(G2_BLOCK, 1) void gemm2_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + wr * 128 + i * 16 + lg * 4 + r;
+      // two column tiles per step: one packed convert rounds both values,
+      // each half goes out with the same 2-byte store to the same address
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < 4; j += 2) {
         const int n = n0 + wc * 64 + j * 16 + lm;
-        float v = acc[i][j][r];
-        if (EPI != G2_EPI_NONE) v += bv[j];
+        float v0 = acc[i][j][r], v1 = acc[i][j + 1][r];
+        if (EPI != G2_EPI_NONE) { v0 += bv[j]; v1 += bv[j + 1]; }
         if (EPI == G2_EPI_BIAS_GELU) {
-          if (STORE_Z) Z[(size_t)m * ldc + n] = f32_to_bf16(v);
-          v = gelu_f(v);
+          if (STORE_Z) {
+            const unsigned int z2 = f32x2_to_bf16x2(v0, v1);
+            Z[(size_t)m * ldc + n] = (ushort_t)z2;
+            Z[(size_t)m * ldc + n + 16] = (ushort_t)(z2 >> 16);
+          }
+          v0 = gelu_f(v0);
+          v1 = gelu_f(v1);
         }
-        C[(size_t)m * ldc + n] = f32_to_bf16(v);
+        const unsigned int c2 = f32x2_to_bf16x2(v0, v1);
+        C[(size_t)m * ldc + n] = (ushort_t)c2;
+        C[(size_t)m * ldc + n + 16] = (ushort_t)(c2 >> 16);
       }
     }
   }
@@ -379,17 +388,19 @@ __global__ __launch_bounds__(256) void gemm2_reduce_kernel(
     for (int r = 0; r < 4; ++r) s[r] += p[r];
   }
   const int m = (int)(i4 / N), n = (int)(i4 % N);
+  float v[4];
   ushort4_t o, zo;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float v = s[r];
-    if (EPI != G2_EPI_NONE) v += bf16_to_f32(bias[n + r]);
-    if (EPI == G2_EPI_BIAS_GELU) {
-      if (STORE_Z) zo[r] = f32_to_bf16(v);
-      v = gelu_f(v);
-    }
-    o[r] = f32_to_bf16(v);
+    v[r] = s[r];
+    if (EPI != G2_EPI_NONE) v[r] += bf16_to_f32(bias[n + r]);
   }
+  if (EPI == G2_EPI_BIAS_GELU) {
+    if (STORE_Z) zo = f32x4_to_bf16x4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
+  }
+  o = f32x4_to_bf16x4(v[0], v[1], v[2], v[3]);
   *(ushort4_t*)(C + (size_t)m * ldc + n) = o;
   if (EPI == G2_EPI_BIAS_GELU && STORE_Z) *(ushort4_t*)(Z + (size_t)m * ldc + n) = zo;
 }

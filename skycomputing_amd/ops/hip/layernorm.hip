@@ -256,7 +256,22 @@ SKY_EXPORT int sky_layernorm_fwd(uint64_t stream, uint64_t x, uint64_t res,
 //
 // NS = 0 (SKY_LN_SPLIT_WB) is the dx pass alone: no accumulators, no LDS
 // merge, and scratch is not touched.
-template <int DT, bool HAS_RES, bool DROP, int CH, int NS>
+//
+// PMERGE (CH <= 2 only) merges in one barrier: every wave writes its
+// NS x CH*512 partials to an LDS region of its own (4 x 12 KB at NS = 3),
+// and after the barrier each thread sums its columns over waves 0, 1, 2, 3
+// in that order from 0.f, which is the order and the arithmetic of the
+// serial merge (zeroed LDS, then the waves add in turn), and stores the
+// slab values from registers, 16 bytes at a time. The serial merge costs
+// five barriers and three passes over the LDS image; it stays for CH = 4,
+// whose four regions would need 96 KB, and under SKY_LN_MERGE_SERIAL=1.
+// So do the kernels without dropout: at 114 to 128 VGPRs they run four
+// blocks per CU, the region writes cost them the registers for that
+// (132 to 138) and four 48 KB regions would not fit the 160 KB of LDS
+// either, and the merge is not worth a block of occupancy. With dropout the
+// VGPRs (130 to 158) allow three blocks with either merge.
+#define LN_PMERGE_OK(DROP, CH, NS) ((CH) <= 2 && (NS) > 0 && (DROP))
+template <int DT, bool HAS_RES, bool DROP, int CH, int NS, bool PMERGE = false>
 __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
     const void* __restrict__ dy, const void* __restrict__ x,
     const void* __restrict__ res, const void* __restrict__ w,
@@ -332,7 +347,58 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_cs_kernel(
       }
     }
   }
-  if constexpr (NS > 0) {
+  if constexpr (NS > 0 && PMERGE) {
+    static_assert(LN_PMERGE_OK(DROP, CH, NS), "see LN_PMERGE_OK");
+    __shared__ __attribute__((aligned(16))) float part[4][NS][CH * 512];
+    // The partials pass through an opaque register constraint first, so
+    // that the 16-byte LDS writes below do not reach back into the row loop:
+    // with contraction on, the SLP vectoriser would otherwise pair that
+    // loop's accumulations by these vectors and fuse other multiplies into
+    // FMAs than the serial-merge kernel does (see RNG_DROP8 in common.h),
+    // and the fp32 kernels' slabs would move by an ulp. What the vectoriser
+    // does is the compiler's choice, not the language's:
+    // tests/test_ln_merge_gpu.py compares this kernel's slabs and outputs
+    // with the serial kernel's, bit for bit, fp32 included, and is what
+    // notices if a compiler decides otherwise.
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        asm volatile("" : "+v"(sw[c][j]), "+v"(sb[c][j]));
+        if constexpr (NS == 3) asm volatile("" : "+v"(sx[c][j]));
+      }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int64_t i8 = (int64_t)c * WAVE + lane;
+      if (i8 < cols8) {
+        float4_t* pw = (float4_t*)&part[wid][0][i8 * 8];
+        float4_t* pb = (float4_t*)&part[wid][1][i8 * 8];
+        pw[0] = float4_t{sw[c][0], sw[c][1], sw[c][2], sw[c][3]};
+        pw[1] = float4_t{sw[c][4], sw[c][5], sw[c][6], sw[c][7]};
+        pb[0] = float4_t{sb[c][0], sb[c][1], sb[c][2], sb[c][3]};
+        pb[1] = float4_t{sb[c][4], sb[c][5], sb[c][6], sb[c][7]};
+        if constexpr (NS == 3) {
+          float4_t* px = (float4_t*)&part[wid][2][i8 * 8];
+          px[0] = float4_t{sx[c][0], sx[c][1], sx[c][2], sx[c][3]};
+          px[1] = float4_t{sx[c][4], sx[c][5], sx[c][6], sx[c][7]};
+        }
+      }
+    }
+    __syncthreads();
+    // cols % 8 == 0, so a row of the slab is cols / 4 whole float4s, all of
+    // them written above (i8 < cols8 covers every column below cols)
+    float* base = scratch + (int64_t)blockIdx.x * NS * cols8 * 8;
+    const int n4 = (int)(cols8 * 2);
+    for (int i4 = threadIdx.x; i4 < n4; i4 += 256) {
+#pragma unroll
+      for (int v = 0; v < NS; ++v) {
+        float4_t a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a += *(const float4_t*)&part[k][v][i4 * 4];
+        *(float4_t*)(base + (int64_t)v * cols8 * 8 + (int64_t)i4 * 4) = a;
+      }
+    }
+  } else if constexpr (NS > 0) {
     // merge the 4 waves' partials through LDS (halves the slab count vs
     // per-wave slabs -> half the scratch the final stage must re-read),
     // then ONE slab write per block.
@@ -529,16 +595,31 @@ static int64_t ln_bwd_dx_launch(const LnBwdArgs& a) {
   }
   unsigned grid = (unsigned)((a.rows + 3) / 4);
   if (grid > gmax) grid = gmax;
+  // one-barrier merge where LN_PMERGE_OK allows it; SKY_LN_MERGE_SERIAL set
+  // (to any value, as with SKY_LN_SPLIT_WB) keeps the serial merge for A/B,
+  // and so does a scratch that the 16-byte slab stores could not address
+  [[maybe_unused]] const bool serial =
+      NS > 0 &&
+      (getenv("SKY_LN_MERGE_SERIAL") != nullptr || (a.scratch & 15) != 0);
   dispatch_tags<NS == 3 ? LN_XSUM_MAXCH : LN_MAXCH>(
       a.dt, a.res != 0, a.keep < 1.f, ln_chunks(a.cols),
       [&](auto DT, auto HR, auto DR, auto CH) {
-        hipLaunchKernelGGL((ln_bwd_dx_cs_kernel<DT, HR, DR, CH, NS>),
-                           dim3(grid), dim3(256), 0, a.s, (const void*)a.dy,
-                           (const void*)a.x, (const void*)a.res,
-                           (const void*)a.w, (const float*)a.mean,
-                           (const float*)a.rstd, (void*)a.dx, (void*)a.dres,
-                           (float*)a.scratch, a.rows, a.cols, a.keep, a.salt,
-                           (const unsigned long long*)a.state);
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, a.s,
+                             (const void*)a.dy, (const void*)a.x,
+                             (const void*)a.res, (const void*)a.w,
+                             (const float*)a.mean, (const float*)a.rstd,
+                             (void*)a.dx, (void*)a.dres, (float*)a.scratch,
+                             a.rows, a.cols, a.keep, a.salt,
+                             (const unsigned long long*)a.state);
+        };
+        if constexpr (LN_PMERGE_OK(DR, CH, NS)) {
+          if (!serial) {
+            launch(ln_bwd_dx_cs_kernel<DT, HR, DR, CH, NS, true>);
+            return;
+          }
+        }
+        launch(ln_bwd_dx_cs_kernel<DT, HR, DR, CH, NS, false>);
       });
   return (int64_t)grid;
 }

@@ -43,10 +43,10 @@ template <int DT>
 DEV void nt_store8(void* p, int64_t i8, const float f[8]);
 template <>
 DEV void nt_store8<DT_BF16>(void* p, int64_t i8, const float f[8]) {
-  ushort8_t v;
+  uint4_t v;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(f[j]);
-  __builtin_nontemporal_store(v, (ushort8_t*)p + i8);
+  for (int j = 0; j < 4; ++j) v[j] = f32x2_to_bf16x2(f[2 * j], f[2 * j + 1]);
+  __builtin_nontemporal_store(v, (uint4_t*)p + i8);
 }
 template <>
 DEV void nt_store8<DT_F32>(void* p, int64_t i8, const float f[8]) {

@@ -81,6 +81,7 @@ def _register_signatures(lib):
         "sky_hblt_linear_gelu_aux": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i32, i32],  # strm x w bias y aux M N K dt aux_dt
         "sky_mfma_probe": [u64, u64, u64, u64],  # strm A B D
         "sky_glds_probe": [u64, u64, u64, i32],
+        "sky_probe_bf16_round": [u64, u64],  # strm counts (3 x uint64, device)
         "sky_gemm": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32],
         # strm A B C bias Z | M N K lda ldb ldc | transA transB epi dt use_glds
         "sky_gemm2": [u64, u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32],

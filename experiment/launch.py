@@ -44,6 +44,13 @@ def build_layer_cfgs(model_config: dict) -> list[dict]:
             dict(model_config.get("bert_config", {})),
             num_class=model_config.get("num_class", 3),
         )
+    if kind == "bert_mlm":
+        from skycomputing_amd.models import bert_pretraining_pipeline_config
+
+        return bert_pretraining_pipeline_config(
+            model_config["num_encoder_layers"],
+            dict(model_config.get("bert_config", {})),
+        )
     if kind == "resnet":
         from skycomputing_amd.models import resnet_pipeline_config
 
@@ -63,7 +70,7 @@ def main():
         Allocator, DeviceBenchmarker, ModelBenchmarker, WorkerManager,
     )
     from skycomputing_amd.logger import Logger
-    from skycomputing_amd.optim import build_optimizer
+    from skycomputing_amd.optim import build_loss, build_optimizer
     from skycomputing_amd.parallel import PartitionPlan, PipelineEngine, init_distributed
     from skycomputing_amd.runner import Runner
     from skycomputing_amd.stimulator import Stimulator
@@ -141,14 +148,15 @@ def main():
                 wm.assign_model_to_worker(r, rng)
 
     sd = float(extra[rank].get("slowdown") or 0.0)
+    # train_config.loss: type="CrossEntropy" (default, also when the key is
+    # missing) | "MaskedLM"; the other keys are the builder's
+    loss_fn = build_loss(cfg.train_config.get("loss"))
     if virtual > 1:
         from skycomputing_amd.parallel.interleaved import InterleavedPipelineEngine
 
         engine = InterleavedPipelineEngine(
             comm, layer_cfgs, plan,
-            loss_fn=lambda logits, labels: torch.nn.functional.cross_entropy(
-                logits.float(), labels
-            ),
+            loss_fn=loss_fn,
             dtype=dtype,
             stage_kwargs=dict(record_forward_time=True, slowdown=sd,
                               mem_limit=extra[rank].get("mem_limit")),
@@ -156,9 +164,7 @@ def main():
     else:
         engine = PipelineEngine(
             comm, layer_cfgs, plan,
-            loss_fn=lambda logits, labels: torch.nn.functional.cross_entropy(
-                logits.float(), labels
-            ),
+            loss_fn=loss_fn,
             dtype=dtype,
             stage_kwargs=dict(record_forward_time=True, slowdown=sd,
                               mem_limit=extra[rank].get("mem_limit")),

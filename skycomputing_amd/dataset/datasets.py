@@ -103,6 +103,61 @@ class SyntheticGlueDataset(Dataset):
 
 
 @DATASET.register_module
+class SyntheticMlmDataset(Dataset):
+    """Deterministic masked-LM pretraining data in SyntheticGlueDataset's
+    shapes: seeded token ids with a random padded tail ([PAD] = 0 there).
+
+    A ``mlm_probability`` share of the non-pad positions is chosen; of
+    those 80 % become ``mask_token_id``, 10 % a random id and 10 % keep
+    their id (BERT's recipe). ``labels`` [S] int64 hold the original id at
+    the chosen positions and -100 (the loss's ignore index) elsewhere.
+    Samples are ``((input_ids, token_type_ids, attention_mask), labels)``,
+    the argument order of BertEmbeddings. ``original_ids`` keeps the
+    unmasked ids."""
+
+    IGNORE_INDEX = -100
+
+    def __init__(
+        self,
+        size: int = 4096,
+        max_seq_length: int = 128,
+        vocab_size: int = 30522,
+        mlm_probability: float = 0.15,
+        mask_token_id: int | None = None,
+        seed: int = 0,
+    ):
+        if not 0.0 <= mlm_probability <= 1.0:
+            raise ValueError(f"mlm_probability {mlm_probability} outside [0, 1]")
+        g = torch.Generator().manual_seed(seed)
+        S = max_seq_length
+        if mask_token_id is None:
+            mask_token_id = min(103, vocab_size - 1)  # bert-base-uncased's [MASK]
+        ids = torch.randint(0, vocab_size, (size, S), generator=g)
+        lengths = torch.randint(S // 2, S + 1, (size,), generator=g)
+        ar = torch.arange(S)[None, :]
+        self.attention_mask = (ar < lengths[:, None]).long()
+        seg = torch.randint(S // 4, max(3 * S // 4, S // 4 + 1), (size,), generator=g)
+        self.token_type_ids = (ar >= seg[:, None]).long() * self.attention_mask
+        ids = ids * self.attention_mask
+        self.original_ids = ids
+        chosen = (torch.rand(size, S, generator=g) < mlm_probability) & self.attention_mask.bool()
+        self.labels = torch.where(chosen, ids, torch.full_like(ids, self.IGNORE_INDEX))
+        u = torch.rand(size, S, generator=g)
+        random_ids = torch.randint(0, vocab_size, (size, S), generator=g)
+        inp = torch.where(chosen & (u < 0.8), torch.full_like(ids, mask_token_id), ids)
+        self.input_ids = torch.where(chosen & (u >= 0.8) & (u < 0.9), random_ids, inp)
+
+    def __len__(self):
+        return self.input_ids.shape[0]
+
+    def __getitem__(self, i):
+        return (
+            (self.input_ids[i], self.token_type_ids[i], self.attention_mask[i]),
+            self.labels[i],
+        )
+
+
+@DATASET.register_module
 class GlueDataset(Dataset):
     """GLUE task dataset (reference: scaelum/dataset/bert_dataset.py:16-94).
 

@@ -4,19 +4,21 @@ from .bert_layers import (
     BertLayerBody,
     BertLayerHead,
     BertLayerTail,
+    BertLMHead,
     BertPooler,
     BertSelfAttention,
     BertTailForClassification,
     LinearActivation,
     SkyLayerNorm,
     bert_pipeline_config,
+    bert_pretraining_pipeline_config,
 )
 from .resnet import ResHead, ResLayer, ResTail, resnet_pipeline_config
 
 __all__ = [
     "BertConfig", "BertEmbeddings", "BertLayerHead", "BertLayerBody",
-    "BertLayerTail", "BertPooler", "BertTailForClassification",
+    "BertLayerTail", "BertLMHead", "BertPooler", "BertTailForClassification",
     "BertSelfAttention", "LinearActivation", "SkyLayerNorm",
-    "bert_pipeline_config", "ResHead", "ResLayer", "ResTail",
-    "resnet_pipeline_config",
+    "bert_pipeline_config", "bert_pretraining_pipeline_config",
+    "ResHead", "ResLayer", "ResTail", "resnet_pipeline_config",
 ]

@@ -22,6 +22,7 @@ Dataflow tuples between pipeline stages:
   BertLayer_Tail(attn_out, interm, ext_mask)-> (hidden', ext_mask)
   BertPooler(hidden, ext_mask)              -> pooled [B, H]
   BertTailForClassification(pooled)         -> logits [B, C]
+  BertLMHead(hidden, ext_mask)              -> logits [B, S, Vpad]  (pretraining)
 """
 
 from __future__ import annotations
@@ -340,6 +341,59 @@ class BertTailForClassification(nn.Module):
 
     def activation_numel(self, batch: int, seq: int) -> int:
         return batch * self.num_class
+
+
+@LAYER.register_module
+class BertLMHead(nn.Module):
+    """Masked-LM head: dense + gelu, LayerNorm, decoder to the vocabulary.
+    (hidden [B, S, H], ext_mask) -> logits [B, S, Vpad].
+
+    Vpad is vocab_size rounded up to a multiple of 64 (30522 -> 30528) so
+    that the decoder GEMM sees an aligned N; columns vocab_size..Vpad-1 are
+    padding, and ``num_classes`` (= vocab_size) is what the loss must be
+    told (ops.softmax_cross_entropy(..., num_classes=head.num_classes)):
+    the pad columns then stay out of the softmax and get gradient 0.
+
+    The decoder weight is NOT tied to BertEmbeddings.word_embeddings: the
+    two live on the first and the last pipeline stage, usually on different
+    ranks, and tying across ranks is out of scope."""
+
+    def __init__(self, config):
+        super().__init__()
+        config = _cfg(config)
+        self.config = config
+        H = config.hidden_size
+        self.num_classes = int(config.vocab_size)
+        self.padded_vocab = (self.num_classes + 63) // 64 * 64
+        self.transform = LinearActivation(H, H, act="gelu")
+        self.layer_norm = SkyLayerNorm(H, config.layer_norm_eps)
+        self.decoder = SkyLinear(H, self.padded_vocab)
+
+    def forward(self, hidden, ext_mask=None):
+        return self.decoder(self.layer_norm(self.transform(hidden)))
+
+    def layer_flops(self, batch: int, seq: int) -> float:
+        H = self.config.hidden_size
+        return 2.0 * batch * seq * H * H + 2.0 * batch * seq * H * self.padded_vocab
+
+    def activation_numel(self, batch: int, seq: int) -> int:
+        return batch * seq * (2 * self.config.hidden_size + self.padded_vocab)
+
+
+def bert_pretraining_pipeline_config(
+    num_encoder_layers: int,
+    bert_config: dict | None = None,
+) -> list[dict]:
+    """The layer-config list of an N-encoder-layer BERT with the masked-LM
+    head: embeddings, N x (Head, Body, Tail), BertLMHead."""
+    bc = dict(bert_config or {})
+    layers: list[dict] = [dict(layer_type="BertEmbeddings", config=bc)]
+    for _ in range(num_encoder_layers):
+        layers.append(dict(layer_type="BertLayer_Head", config=bc))
+        layers.append(dict(layer_type="BertLayer_Body", config=bc))
+        layers.append(dict(layer_type="BertLayer_Tail", config=bc))
+    layers.append(dict(layer_type="BertLMHead", config=bc))
+    return layers
 
 
 def bert_pipeline_config(

@@ -25,7 +25,7 @@ __all__ = [
     "layer_norm", "bias_gelu", "bias_tanh", "masked_softmax", "dropout",
     "attention_context", "attention_block", "ffn_block", "linear_act",
     "linear_residual_layer_norm",
-    "embedding_fused", "sgd_step", "adamw_step",
+    "embedding_fused", "softmax_cross_entropy", "sgd_step", "adamw_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
 ]
 
@@ -332,6 +332,48 @@ def embedding_fused(
         input_ids, token_type_ids, position_ids,
         word_emb, pos_emb, type_emb, ln_weight, ln_bias, eps,
     )
+
+
+def softmax_cross_entropy(logits, labels, ignore_index: int = -100,
+                          num_classes: int | None = None,
+                          inplace_backward: bool = False):
+    """Mean softmax cross-entropy over the valid rows: a 0-dim fp32 loss.
+
+    logits [..., ld] and labels [...] are flattened to rows. Columns
+    num_classes..ld-1 are padding (None: ld classes): never part of the
+    softmax, gradient 0. A row is valid iff 0 <= label < num_classes and
+    label != ignore_index; EVERY other label ignores its row, an
+    out-of-range one included (nothing validates labels on the host, which
+    would synchronise). With no valid row the loss is 0 and the gradient
+    zero, where torch returns NaN.
+
+    GPU, fp32/bf16: SoftmaxCrossEntropyFn, two row kernels and a one-block
+    finish (ops/hip/xent.hip). The logits are read once forward and once
+    backward, ignored rows not at all; by byte count that is 0.75 GB where
+    cross_entropy(logits.float(), labels) moves at least 3.5 GB at
+    [4096, 30522] bf16; measured there on an MI355X, forward + backward
+    take 245 us against 1160 us, with 250 MB instead of 1500 MB above the
+    logits (profiles/r10_notes.md). The valid count stays on the device: no
+    synchronisation, and a captured step follows new labels under replay.
+
+    inplace_backward=True writes the gradient over the logits' own storage
+    instead of allocating a second [N, ld] buffer. That is safe only when
+    nothing else reads the logits after this loss — true for the output of a
+    linear layer, whose backward needs its input and weight but not its
+    output; false if the logits are also returned, logged, or fed to another
+    op that saves them. Off by default.
+
+    CPU, other dtypes and SKY_ALLOW_EAGER_GPU=1 run ops/eager.py with the
+    same semantics."""
+    if logits.dtype in (torch.float32, torch.bfloat16) and _use_hip(logits):
+        from .functions import SoftmaxCrossEntropyFn
+
+        V = logits.shape[-1] if num_classes is None else int(num_classes)
+        return SoftmaxCrossEntropyFn.apply(
+            logits, labels, V, int(ignore_index), bool(inplace_backward))
+    if logits.is_cuda:
+        _use_hip(logits)  # a missing extension still fails loudly
+    return eager.softmax_cross_entropy(logits, labels, ignore_index, num_classes)
 
 
 def sgd_step(params, grads, lr, momentum=0.0, weight_decay=0.0,

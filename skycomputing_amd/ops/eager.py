@@ -127,6 +127,42 @@ def embedding_fused(
     return layer_norm(e, ln_weight, ln_bias, eps)
 
 
+def softmax_cross_entropy(
+    logits: torch.Tensor,
+    labels: torch.Tensor,
+    ignore_index: int = -100,
+    num_classes: int | None = None,
+) -> torch.Tensor:
+    """Mean cross-entropy over the valid rows of logits [..., ld], fp32,
+    0-dim; the semantics of the HIP kernels (ops/hip/xent.hip):
+
+      * columns num_classes..ld-1 are padding: sliced off, gradient 0;
+      * a row is valid iff 0 <= label < num_classes and
+        label != ignore_index; any other label ignores the row (torch
+        raises on an out-of-range label);
+      * no valid row gives loss 0 and zero gradients (torch gives NaN);
+      * ignored rows contribute nothing whatever they hold.
+    """
+    ld = logits.shape[-1]
+    V = ld if num_classes is None else int(num_classes)
+    if not 1 <= V <= ld:
+        raise ValueError(f"num_classes {V} outside 1..{ld}")
+    if labels.shape != logits.shape[:-1]:
+        raise ValueError(
+            f"labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+    z = logits.reshape(-1, ld)[:, :V].float()
+    lab = labels.reshape(-1).to(torch.int64)
+    valid = (lab >= 0) & (lab < V) & (lab != ignore_index)
+    # ignored rows are replaced, not multiplied by 0: a NaN there stays out
+    # of the loss and of the gradient
+    z = z.masked_fill(~valid[:, None], 0.0)
+    rowloss = F.cross_entropy(z, torch.where(valid, lab, torch.zeros_like(lab)),
+                              reduction="none")
+    rowloss = torch.where(valid, rowloss, torch.zeros_like(rowloss))
+    count = valid.sum()
+    return rowloss.sum() / count.clamp(min=1).to(rowloss.dtype)
+
+
 @torch.no_grad()
 def sgd_step(
     params: list[torch.Tensor],

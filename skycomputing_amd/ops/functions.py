@@ -1169,3 +1169,92 @@ class EmbeddingFusedFn(torch.autograd.Function):
             dwe.to(word_emb.dtype), dpe.to(pos_emb.dtype), dte.to(type_emb.dtype),
             dlnw.to(ln_w.dtype), dlnb.to(ln_w.dtype), None,
         )
+
+
+def xent_forward(logits2, labels1, num_classes: int, ignore_index: int):
+    """The forward launches of softmax cross-entropy (ops/hip/xent.hip) on
+    logits2 [N, ld] (contiguous, fp32/bf16) and labels1 [N] (int64):
+    sky_xent_fwd, then sky_xent_finish. Returns fp32
+    (rowmax [N], logsum [N], rowloss [N], block [2]) with
+    block = {mean loss over valid rows, 1 / valid count}, both 0 when no row
+    is valid. Nothing here synchronises or depends on the labels' values."""
+    lib = hiplib.require()
+    N, ld = logits2.shape
+    dev = logits2.device
+    stats = torch.empty(3, N, dtype=torch.float32, device=dev)
+    block = torch.empty(2, dtype=torch.float32, device=dev)
+    rowmax, logsum, rowloss = stats[0], stats[1], stats[2]
+    check(
+        lib.sky_xent_fwd(
+            _stream(), ptr(logits2), ptr(labels1), ptr(rowmax), ptr(logsum),
+            ptr(rowloss), N, num_classes, ld, ignore_index, _dt(logits2)),
+        "sky_xent_fwd",
+    )
+    check(
+        lib.sky_xent_finish(
+            _stream(), ptr(rowloss), ptr(labels1), ptr(block), N, num_classes,
+            ignore_index),
+        "sky_xent_finish",
+    )
+    return rowmax, logsum, rowloss, block
+
+
+class SoftmaxCrossEntropyFn(torch.autograd.Function):
+    """Mean softmax cross-entropy over the valid rows of logits [..., ld]
+    (classes 0..num_classes-1, the rest padding) in two row kernels and a
+    one-block finish (ops/hip/xent.hip). The valid count and its reciprocal
+    stay on the device, and backward reads the incoming gradient from
+    device memory too, so the node makes no synchronisation and replays
+    correctly in a hipGraph when the labels change.
+
+    With inplace_backward the gradient is written over the saved logits and
+    returned as an alias of them: right only when nothing else reads the
+    logits after this loss (see ops.softmax_cross_entropy)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, num_classes, ignore_index, inplace_backward):
+        ld = logits.shape[-1]
+        if not 1 <= num_classes <= ld:
+            raise ValueError(f"num_classes {num_classes} outside 1..{ld}")
+        if labels.shape != logits.shape[:-1]:
+            raise ValueError(
+                f"labels {tuple(labels.shape)} do not match logits "
+                f"{tuple(logits.shape)}")
+        logits2 = logits.reshape(-1, ld)
+        if not logits2.is_contiguous():
+            if inplace_backward:
+                raise ValueError("inplace_backward needs contiguous logits")
+            logits2 = logits2.contiguous()
+        labels1 = labels.reshape(-1).to(torch.int64).contiguous()
+        rowmax, logsum, _, block = xent_forward(
+            logits2, labels1, num_classes, ignore_index)
+        ctx.save_for_backward(logits2, labels1, rowmax, logsum, block)
+        ctx.args = (num_classes, ignore_index, inplace_backward)
+        ctx.shape = logits.shape
+        return block[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = hiplib.require()
+        logits2, labels1, rowmax, logsum, block = ctx.saved_tensors
+        num_classes, ignore_index, inplace = ctx.args
+        N, ld = logits2.shape
+        gout = gout.to(torch.float32).contiguous()
+        if inplace:
+            dlogits = logits2.detach()
+        else:
+            # the kernel splits rows into head/body/tail once for loads and
+            # stores: give the output the logits' offset from a 16-byte line
+            es = logits2.element_size()
+            off = (logits2.data_ptr() % 16) // es
+            flat = torch.empty(N * ld + off, dtype=logits2.dtype,
+                               device=logits2.device)
+            dlogits = flat[off:].view(N, ld)
+        check(
+            lib.sky_xent_bwd(
+                _stream(), ptr(logits2), ptr(labels1), ptr(rowmax),
+                ptr(logsum), ptr(block), ptr(gout), ptr(dlogits), N,
+                num_classes, ld, ignore_index, _dt(logits2)),
+            "sky_xent_bwd",
+        )
+        return dlogits.view(ctx.shape), None, None, None, None

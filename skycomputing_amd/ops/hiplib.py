@@ -70,6 +70,13 @@ def _register_signatures(lib):
         "sky_gradnorm_finish": [u64, u64, i64, u64, f32],  # strm partials n hyper max_norm
         "sky_adamw_step": [u64, u64, i64, u64, f64, f64, f32, f32, i32, i32],
         #                  strm descs n   hyper b1   b2   eps  wd   dt   flags
+        "sky_xent_fwd": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i32],
+        #                strm logits labels rowmax logsum rowloss N V ld ignore dt
+        "sky_xent_finish": [u64, u64, u64, u64, i64, i64, i64],
+        #                   strm rowloss labels block N V ignore
+        "sky_xent_bwd": [u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i32],
+        # strm logits labels rowmax logsum block gout dlogits | N V ld ignore dt
+        # (block: 2 x fp32 on the device, {mean loss, 1/valid count})
         "sky_detect_mem": [u64, u64],  # free_out, total_out (host ptrs)
         "sky_dropout_fwd": [u64, u64, u64, i64, f32, u64, u64, i32],
         #                   strm  x    y    n   keep salt state dt

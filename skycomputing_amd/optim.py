@@ -295,6 +295,49 @@ class FusedAdamW:
                 m.copy_(s.to(m.device))
 
 
+def _classification_loss():
+    def loss_fn(logits, labels):
+        return torch.nn.functional.cross_entropy(logits.float(), labels)
+
+    return loss_fn
+
+
+def _masked_lm_loss(num_classes: int | None = None, ignore_index: int = -100,
+                    inplace_backward: bool = False):
+    def loss_fn(logits, labels):
+        return ops.softmax_cross_entropy(
+            logits, labels, ignore_index=ignore_index, num_classes=num_classes,
+            inplace_backward=inplace_backward)
+
+    return loss_fn
+
+
+LOSSES = {"CrossEntropy": _classification_loss, "MaskedLM": _masked_lm_loss}
+
+
+def build_loss(cfg: dict | None = None):
+    """Build ``loss_fn(logits, labels)`` from a config dict: ``type`` names
+    it, every other key goes to its builder.
+
+    ``"CrossEntropy"`` (also when ``cfg`` is empty or None) is the
+    classification loss, ``cross_entropy(logits.float(), labels)``.
+    ``"MaskedLM"`` takes ``num_classes`` (the vocabulary size; the logits'
+    further columns are padding), ``ignore_index`` and ``inplace_backward``
+    and calls ops.softmax_cross_entropy: the mean over the labelled tokens.
+
+    With microbatches the engines average these per-microbatch means, and
+    scale each backward by 1/M. For MaskedLM the step loss is therefore the
+    mean of per-microbatch valid-token means, which weights a token of a
+    sparsely labelled microbatch more than the mean over all of the step's
+    labelled tokens would; a microbatch with no labelled token counts as 0."""
+    kwargs = dict(cfg or {})
+    kind = kwargs.pop("type", "CrossEntropy")
+    if kind not in LOSSES:
+        raise ValueError(
+            f"unknown loss type {kind!r}; known types: {sorted(LOSSES)}")
+    return LOSSES[kind](**kwargs)
+
+
 OPTIMIZERS = {"SGD": FusedSGD, "AdamW": FusedAdamW}
 
 

@@ -344,7 +344,11 @@ def _attn_bwd_scratch(qkv):
     """The two-kernel backward's transposed scratch (pdT, dsT), [B,h,S,S]
     each. bwd2 loads whole 32-q fragments, so for S % 32 != 0 the last
     row's load runs past the tensor; zero B rows null it only if those
-    bytes are finite -> zeroed tail."""
+    bytes are finite -> zeroed tail.
+    The default keys-on-rows pair keeps P and dS in registers and uses only
+    the head of pdT, for the fp32 row dots [B*h*S] its dQ kernel hands to its
+    dK/dV kernel; SKY_ATTN_KROWS=0 (and S = 1) runs bwd1s + bwd2, which fill
+    both tensors."""
     B, S, _, h, _ = qkv.shape
     alloc = torch.empty if S == 128 else torch.zeros
     n = B * h * S * S + (32 if S % 32 else 0)
@@ -358,8 +362,9 @@ class FusedAttentionFn(torch.autograd.Function):
     materialized in forward (row max/sum saved, flash-style).
 
     Backward default: TWO fused MFMA kernels (sky_attn_bwd,
-    ops/hip/attention_bwd.hip) — recompute + dS + dQ, then dK/dV over
-    transposed scratch — no torch ops at all.
+    ops/hip/attention_bwd.hip) — recompute + dS + dQ, then dK/dV from a
+    second recompute (SKY_ATTN_KROWS=0: over transposed scratch) — no torch
+    ops at all.
     SKY_NO_FUSED_ATTN_BWD=1 selects the decomposed fallback (sky_attn_probs
     recompute + hipBLASLt batched GEMMs + HIP softmax-backward).
 

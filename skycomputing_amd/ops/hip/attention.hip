@@ -21,6 +21,9 @@
 //
 // Fragment mappings verified on hardware by sky_mfma_probe
 // (tests/test_ops_gpu.py::test_mfma_layout).
+//
+// attn_fwd_kernel (the structure above) serves probs mode and
+// SKY_ATTN_KROWS=0; the default forward is attn_fwd_krows_kernel below.
 
 #include "attn_common.h"
 
@@ -250,6 +253,135 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(
     att_store_rows16(obase, h * ATT_D, oacc[qi], (qt0 + qi) * 16, S, lm, lg);
 }
 
+// ---------------------------------------------------------------------------
+// Forward with the KEYS on the MFMA rows (the default; SKY_ATTN_KROWS=0
+// restores attn_fwd_kernel). S^T = K Q^T comes out of the MFMA with a lane
+// holding four consecutive keys of ONE query, which is a B operand of
+// O^T = V^T Pd^T as it stands (att_pack_dpair), so P never goes to LDS:
+//   * K and V are both staged up front by glds, one barrier in the kernel;
+//   * m, l are per-lane scalars: the lane's own registers + two shuffles;
+//   * O^T leaves a lane with four consecutive d of its token: 8-byte stores.
+// One block per (b, h, 64*QPW-query block); a wave owns QPW 16-query tiles
+// 64 queries apart. LDS: K [128][64] sw7 @0, V @16K, key mask fp32 @32K.
+#define KR_K_OFF KR_IMG0_OFF
+#define KR_V_OFF KR_IMG1_OFF
+#define KR_MASK_OFF KR_AUX_OFF
+#define KR_LDS_BYTES (KR_AUX_OFF + 512)
+
+template <bool HAS_MASK, int QPW>
+__global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
+    ushort_t* __restrict__ out, float* __restrict__ m_io,
+    float* __restrict__ l_io, int B, int S, int h, float scale, float keep,
+    uint64_t salt, const unsigned long long* __restrict__ state) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 64 * QPW - 1) / (64 * QPW);
+  const int bh = blockIdx.x / QB;
+  const int qb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int NT = (S + 15) / 16;
+  const int NP = (S + 31) / 32;  // key-tile pairs = PV contraction steps
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  float* mk = (float*)lds_at(lds, KR_MASK_OFF);
+
+  // whole tile pairs are staged; tokens >= S re-read token S-1, finite
+  // values that the -3e38 mask (scores) and the zero P (PV) null
+  att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KR_K_OFF, tid);
+  att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KR_V_OFF, tid);
+  att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  ushort_t* obase = out + ((size_t)b * S * h + hh) * ATT_D;
+#pragma clang loop unroll(disable)
+  for (int qi = 0; qi < QPW; ++qi) {
+    const int qtok_base = (qb * QPW + qi) * 64 + w * 16;
+    if (qtok_base >= S) break;
+    const int q = qtok_base + lm;  // this lane's query
+    const int qc = q < S ? q : S - 1;
+    bf16x8 bq[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+      bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+    f32x4 sacc[8];
+    att_zero(sacc);
+    att_score_tile_t(sacc, bq, lds, KR_K_OFF, NT, lm, lg);
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+      const f32x4 mv = att_mask_keys4(mk, mt, lg);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float zz = sacc[mt][r] * scale + mv[r];
+        sacc[mt][r] = zz;
+        mx = fmaxf(mx, zz);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sm = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float p = __expf(sacc[mt][r] - mx);
+        sacc[mt][r] = p;
+        sm += p;
+      }
+    }
+    sm += __shfl_xor(sm, 16, 64);
+    sm += __shfl_xor(sm, 32, 64);
+    const float inv = 1.f / sm;
+    if (lg == 0 && q < S) {
+      m_io[(size_t)bh * S + q] = mx;
+      l_io[(size_t)bh * S + q] = sm;
+    }
+    // normalize + dropout in place; keys >= S hold exact zeros already
+    uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    if (keep < 1.f) att_drop_hash_krows(z, seed, bh, S, q, lg);
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float p = sacc[mt][r] * inv;
+        if (keep < 1.f) p = att_drop_keep(z[r], mt, keep16) ? p * inv_keep : 0.f;
+        sacc[mt][r] = p;
+      }
+    }
+    // O^T = V^T Pd^T: B = the score registers, A = V^T by tr16
+    f32x4 oacc[4];
+    att_zero(oacc);
+#pragma unroll
+    for (int kp = 0; kp < 4; ++kp) {
+      if (kp >= NP) continue;
+      const bf16x8 bp = att_pack_dpair(sacc[2 * kp], sacc[2 * kp + 1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 av = abf_tr_rows64_2(lds, KR_V_OFF, kp * 32 + lg * 4,
+                                          kp * 32 + 16 + lg * 4, ct * 4, lm);
+        oacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oacc[ct], 0, 0, 0);
+      }
+    }
+    att_store_cols16(obase, h * ATT_D, oacc, qtok_base, S, lm, lg);
+  }
+}
+
 // pack dQ/dK/dV (each [B,h,S,d] contiguous) into dqkv [B,S,3,h,d] in one
 // pass — replaces three permute-copies in the attention backward.
 template <int DT>
@@ -317,6 +449,25 @@ static int attn_launch(uint64_t stream, uint64_t qkv, uint64_t mask,
   // SKY_ATTN_TRV=0 restores the old staging for A/B.
   const char* trve = getenv("SKY_ATTN_TRV");
   const bool trv = !(trve && trve[0] == '0');
+  // Default: the keys-on-rows kernel, one block per (b, h, 64-query block).
+  // SKY_ATTN_KROWS=0 restores attn_fwd_kernel; =2 runs the keys-on-rows
+  // kernel with one block per (b, h, 128 queries), K and V staged once per
+  // head, for A/B (profiles/r11_notes.md). Probs mode keeps attn_fwd_kernel.
+  const char* kre = getenv("SKY_ATTN_KROWS");
+  if (!probs_mode && !(kre && kre[0] == '0')) {
+    const bool wide = kre && kre[0] == '2';
+    const int qspan = wide ? 128 : 64;
+    dim3 kgrid((unsigned)(B * h * ((S + qspan - 1) / qspan)));
+#define ATTK(QPW)                                                             \
+  ATT_LAUNCH_HM(hm, (attn_fwd_krows_kernel<HM, QPW>), kgrid, KR_LDS_BYTES, s, \
+                (const ushort_t*)qkv, (const ushort_t*)mask, (ushort_t*)out,  \
+                (float*)m, (float*)lsum, (int)B, (int)S, (int)h, scale, keep, \
+                salt, (const unsigned long long*)state)
+    if (wide) ATTK(2); else ATTK(1);
+#undef ATTK
+    LAUNCH_CHECK();
+    return 0;
+  }
 #define ATT(SML, PM, TRV)                                                     \
   ATT_LAUNCH_HM(hm, (attn_fwd_kernel<HM, SML, PM, TRV>), grid, lds_bytes, s,  \
                 (const ushort_t*)qkv, (const ushort_t*)mask, (ushort_t*)out,  \

@@ -14,6 +14,9 @@
 //
 // Replaces: sky_attn_probs + 4 hipBLASLt bmms + softmax-bwd + dropout-bwd
 // + permute copies + the dqkv pack (FusedAttentionFn.backward fast path).
+//
+// B1 + B2 run with SKY_ATTN_KROWS=0 and for S = 1; the default pair is
+// attn_bwd_dq_krows_kernel + attn_bwd_dkv_krows_kernel further down.
 // ============================================================================
 
 #include "attn_common.h"
@@ -552,6 +555,337 @@ SKY_EXPORT int sky_attn_bwd_fused(uint64_t stream, uint64_t qkv,
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// The default backward pair (SKY_ATTN_KROWS=0 restores bwd1s + bwd2): P and
+// dS stay in the registers their MFMA left them in. Each product is
+// computed in the orientation the next one wants (att_pack_dpair), so no
+// dS tile goes through LDS and no dS^T / Pd^T goes through global scratch;
+// the second kernel recomputes them from Q, K, V, dO and the row statistics.
+//
+// dQ, per (b, h, 64-query block), keys on the MFMA rows: S^T = K Q^T and
+// dPd^T = V dO^T, a lane owns ONE query (m, 1/l and the row dot are lane
+// scalars), P overwrites the scores (one __expf per element), dS^T
+// overwrites them again and is the B operand of dQ^T = K^T dS^T. Also
+// writes dot[bh*S + q] (fp32) for the second kernel, and with DBIAS the
+// block's 64 dQ column sums to slab b*QB + qb like attn_bwd1s_kernel.
+// LDS: K [128][64] sw7 @0, V @16K, key mask fp32 @32K, DBIAS sums @32.5K.
+#define KRB_K_OFF KR_IMG0_OFF
+#define KRB_V_OFF KR_IMG1_OFF
+#define KRB_MASK_OFF KR_AUX_OFF
+#define KRB_SUM_OFF (KR_AUX_OFF + 512)
+#define KRB_DQ_LDS (KR_AUX_OFF + 512 + 1024)
+
+template <bool HAS_MASK, bool DBIAS>
+__global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
+    const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
+    const float* __restrict__ l_io, float* __restrict__ dot_out,
+    ushort_t* __restrict__ dqkv, int B, int S, int h, float scale, float keep,
+    uint64_t salt, const unsigned long long* __restrict__ state,
+    float* __restrict__ dbscr) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 63) / 64;
+  const int bh = blockIdx.x / QB;
+  const int qb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int dots = h * ATT_D;
+  const int NT = (S + 15) / 16;
+  const int NP = (S + 31) / 32;
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D;
+  float* mk = (float*)lds_at(lds, KRB_MASK_OFF);
+
+  const int qtok_base = qb * 64 + w * 16;
+  const bool active = qtok_base < S;
+  const int q = qtok_base + lm;  // this lane's query
+  const int qc = q < S ? q : S - 1;
+
+  att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KRB_K_OFF, tid);
+  att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KRB_V_OFF, tid);
+  att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  bf16x8 bq[2], bdo[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+    bdo[ks] = *(const bf16x8*)(dobase + (size_t)qc * dots + ks * 32 + lg * 8);
+  }
+  const float mrow = m_io[(size_t)bh * S + qc];
+  const float lrow = 1.f / l_io[(size_t)bh * S + qc];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  float cs = 0.f;
+  if (active) {
+    f32x4 sacc[8], dacc[8];
+    att_zero(sacc);
+    att_zero(dacc);
+    att_score_tile_t(sacc, bq, lds, KRB_K_OFF, NT, lm, lg);   // K Q^T
+    att_score_tile_t(dacc, bdo, lds, KRB_V_OFF, NT, lm, lg);  // V dO^T
+    uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    if (keep < 1.f) att_drop_hash_krows(z, seed, bh, S, q, lg);
+    // P -> sacc, dropout-masked dP -> dacc, row dot
+    float dot = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+      const f32x4 mv = att_mask_keys4(mk, mt, lg);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = mt * 16 + lg * 4 + r;
+        const float p = att_prob(sacc[mt][r], scale, mv[r], mrow, lrow,
+                                 q < S && key < S);
+        float dp = dacc[mt][r];
+        if (keep < 1.f)
+          dp = att_drop_keep(z[r], mt, keep16) ? dp * inv_keep : 0.f;
+        dot += dp * p;
+        sacc[mt][r] = p;
+        dacc[mt][r] = dp;
+      }
+    }
+    dot += __shfl_xor(dot, 16, 64);
+    dot += __shfl_xor(dot, 32, 64);
+    if (lg == 0 && q < S) dot_out[(size_t)bh * S + q] = dot;
+    // dS^T over P, then dQ^T = K^T dS^T
+    f32x4 qacc[4];
+    att_zero(qacc);
+#pragma unroll
+    for (int kp = 0; kp < 4; ++kp) {
+      if (kp >= NP) continue;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          sacc[2 * kp + t][r] =
+              scale * sacc[2 * kp + t][r] * (dacc[2 * kp + t][r] - dot);
+      }
+      const bf16x8 bds = att_pack_dpair(sacc[2 * kp], sacc[2 * kp + 1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 ak = abf_tr_rows64_2(lds, KRB_K_OFF, kp * 32 + lg * 4,
+                                          kp * 32 + 16 + lg * 4, ct * 4, lm);
+        qacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, bds, qacc[ct], 0, 0, 0);
+      }
+    }
+    ushort_t* dq = dqkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+    att_store_cols16(dq, ts, qacc, qtok_base, S, lm, lg);
+    if constexpr (DBIAS) cs = att_colsum_cols16(qacc, qtok_base, S, lm);
+  }
+  if constexpr (DBIAS) {
+    // inactive waves contribute their zeros and must reach the barrier too
+    float* wsum = (float*)lds_at(lds, KRB_SUM_OFF);  // [4 waves][64 cols]
+    wsum[w * 64 + att_colsum_cols16_col(lm, lg)] = cs;
+    __syncthreads();
+    if (tid < 64)
+      dbscr[((size_t)b * QB + qb) * ts + (size_t)hh * ATT_D + tid] =
+          (wsum[tid] + wsum[64 + tid]) + (wsum[128 + tid] + wsum[192 + tid]);
+  }
+}
+
+// dK/dV, per (b, h, 64-key block), queries on the MFMA rows, launched after
+// the dQ kernel: a wave owns 16 keys (K and V fragments from global) and
+// walks the queries in pairs of 16-row tiles: S = Q K^T and dPd = dO V^T
+// from the Q / dO images in LDS, P, Pd and dS from the saved m, 1/l and the
+// dQ kernel's dot, and the packed pair is the B operand of
+// dV^T += dO^T Pd and dK^T += Q^T dS. With DBIAS the block writes its dK
+// and dV column sums to slab b*QB + kb: one key block per query block, so
+// every (slab, column) is written exactly once and nothing is zero-filled.
+// LDS: Q [128][64] sw7 @0, dO @16K, m | 1/l | dot fp32 [128] each @32K,
+// keep bits (att_drop_bits_lds) @33.5K, DBIAS sums [4][dK 64 | dV 64] @35.5K.
+#define KRB_Q_OFF KR_IMG0_OFF
+#define KRB_DO_OFF KR_IMG1_OFF
+#define KRB_STAT_OFF KR_AUX_OFF
+#define KRB_BITS_OFF (KR_AUX_OFF + 1536)
+#define KRB_SUM2_OFF (KR_AUX_OFF + 1536 + 2048)
+#define KRB_DKV_LDS (KR_AUX_OFF + 1536 + 2048 + 2048)
+
+template <bool HAS_MASK, bool DBIAS>
+__global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
+    const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
+    const float* __restrict__ l_io, const float* __restrict__ dot_in,
+    ushort_t* __restrict__ dqkv, int B, int S, int h, float scale, float keep,
+    uint64_t salt, const unsigned long long* __restrict__ state,
+    float* __restrict__ dbscr) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 63) / 64;
+  const int bh = blockIdx.x / QB;
+  const int kb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int dots = h * ATT_D;
+  const int NT = (S + 15) / 16;
+  const int NP = (S + 31) / 32;
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D;
+  float* st = (float*)lds_at(lds, KRB_STAT_OFF);
+  unsigned char* bits = (unsigned char*)lds_at(lds, KRB_BITS_OFF);
+
+  const int ktok_base = kb * 64 + w * 16;
+  const bool active = ktok_base < S;
+  const int key = ktok_base + lm;  // this lane's key
+  const int kc = key < S ? key : S - 1;
+
+  att_glds_rows(qbase, ts, 0, NP * 32, true, S, lds, KRB_Q_OFF, tid);
+  att_glds_rows(dobase, dots, 0, NP * 32, true, S, lds, KRB_DO_OFF, tid);
+  // rows >= S: 1/l = 0 and a false valid flag null P, dot = 0 keeps dS finite
+  if (tid < ATT_SMAX) {
+    const bool live = tid < S;
+    st[tid] = live ? m_io[(size_t)bh * S + tid] : 0.f;
+    st[128 + tid] = live ? 1.f / l_io[(size_t)bh * S + tid] : 0.f;
+    st[256 + tid] = live ? dot_in[(size_t)bh * S + tid] : 0.f;
+  }
+  if (keep < 1.f)
+    att_drop_bits_lds(bits, seed, bh, S, kb, NP * 32, keep16, tid);
+  bf16x8 bk[2], bv[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bk[ks] = *(const bf16x8*)(kbase + (size_t)kc * ts + ks * 32 + lg * 8);
+    bv[ks] = *(const bf16x8*)(vbase + (size_t)kc * ts + ks * 32 + lg * 8);
+  }
+  float mv = 0.f;
+  if (HAS_MASK && key < S) mv = bf16_to_f32(mask[(size_t)b * S + key]);
+  if (key >= S) mv = -3.0e38f;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  float ck = 0.f, cv = 0.f;
+  if (active) {
+    f32x4 kacc[4], vacc[4];
+    att_zero(kacc);
+    att_zero(vacc);
+#pragma unroll
+    for (int qp = 0; qp < 4; ++qp) {
+      if (qp >= NP) continue;
+      f32x4 pd[2], ds[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int qt = 2 * qp + t;
+        pd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        ds[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (qt >= NT) continue;
+        const int qrow = qt * 16 + lm;  // < NP*32: a staged (clamped) row
+        f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, d4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const bf16x8 aq = *(const bf16x8*)lds_at(
+              lds, swz(KRB_Q_OFF + qrow * 128 + (ks * 32 + lg * 8) * 2, qrow, 7));
+          const bf16x8 ado = *(const bf16x8*)lds_at(
+              lds, swz(KRB_DO_OFF + qrow * 128 + (ks * 32 + lg * 8) * 2, qrow, 7));
+          s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, bk[ks], s4, 0, 0, 0);
+          d4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado, bv[ks], d4, 0, 0, 0);
+        }
+        const f32x4 m4 = *(const f32x4*)(st + qt * 16 + lg * 4);
+        const f32x4 il4 = *(const f32x4*)(st + 128 + qt * 16 + lg * 4);
+        const f32x4 dot4 = *(const f32x4*)(st + 256 + qt * 16 + lg * 4);
+        unsigned kbits = 0xFFFFFFFFu;
+        if (keep < 1.f)
+          kbits = *(const unsigned*)(bits + ((qt * 4 + lg) * 16 + lm) * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qq = qt * 16 + lg * 4 + r;
+          const float p = att_prob(s4[r], scale, mv, m4[r], il4[r],
+                                   qq < S && key < S);
+          const bool kbit = (kbits >> (8 * r + w)) & 1u;
+          float pdv = p, dp = d4[r];
+          if (keep < 1.f) {
+            pdv = kbit ? p * inv_keep : 0.f;
+            dp = kbit ? dp * inv_keep : 0.f;
+          }
+          pd[t][r] = pdv;
+          ds[t][r] = scale * p * (dp - dot4[r]);
+        }
+      }
+      const bf16x8 bpd = att_pack_dpair(pd[0], pd[1]);
+      const bf16x8 bds = att_pack_dpair(ds[0], ds[1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 adot = abf_tr_rows64_2(lds, KRB_DO_OFF, qp * 32 + lg * 4,
+                                            qp * 32 + 16 + lg * 4, ct * 4, lm);
+        vacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adot, bpd, vacc[ct], 0, 0, 0);
+        const bf16x8 aqt = abf_tr_rows64_2(lds, KRB_Q_OFF, qp * 32 + lg * 4,
+                                           qp * 32 + 16 + lg * 4, ct * 4, lm);
+        kacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aqt, bds, kacc[ct], 0, 0, 0);
+      }
+    }
+    ushort_t* dk = dqkv + (size_t)b * S * ts + (size_t)(h + hh) * ATT_D;
+    ushort_t* dv = dqkv + (size_t)b * S * ts + (size_t)(2 * h + hh) * ATT_D;
+    att_store_cols16(dk, ts, kacc, ktok_base, S, lm, lg);
+    att_store_cols16(dv, ts, vacc, ktok_base, S, lm, lg);
+    if constexpr (DBIAS) {
+      ck = att_colsum_cols16(kacc, ktok_base, S, lm);
+      cv = att_colsum_cols16(vacc, ktok_base, S, lm);
+    }
+  }
+  if constexpr (DBIAS) {
+    float* wsum = (float*)lds_at(lds, KRB_SUM2_OFF);  // [4][dK 64 | dV 64]
+    const int c = att_colsum_cols16_col(lm, lg);
+    wsum[w * 128 + c] = ck;
+    wsum[w * 128 + 64 + c] = cv;
+    __syncthreads();
+    if (tid < 128) {
+      // tid < 64: dK column tid; otherwise dV column tid - 64
+      const size_t col = (size_t)((tid < 64 ? h : 2 * h) + hh) * ATT_D + (tid & 63);
+      dbscr[((size_t)b * QB + kb) * ts + col] =
+          (wsum[tid] + wsum[128 + tid]) + (wsum[256 + tid] + wsum[384 + tid]);
+    }
+  }
+}
+
+// the default pair: dQ + dot, then dK/dV. dot (fp32 [B*h*S]) lives at the
+// head of the pdT scratch the entry points receive (2*S*S bytes per (b,h)
+// cover 4*S for S >= 2); nothing else of pdT / dsT is touched.
+template <bool DBIAS>
+static void launch_attn_bwd_krows(hipStream_t s, uint64_t qkv, uint64_t dout,
+                                  uint64_t mask, uint64_t m, uint64_t lsum,
+                                  uint64_t pdT, uint64_t dqkv, int64_t B,
+                                  int64_t S, int64_t h, float scale,
+                                  float keep, uint64_t salt, uint64_t state,
+                                  float* dbscr) {
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  ATT_LAUNCH_HM(mask != 0, (attn_bwd_dq_krows_kernel<HM, DBIAS>), grid,
+                KRB_DQ_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
+                (float*)pdT, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
+                keep, salt, (const unsigned long long*)state, dbscr);
+  ATT_LAUNCH_HM(mask != 0, (attn_bwd_dkv_krows_kernel<HM, DBIAS>), grid,
+                KRB_DKV_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
+                (const float*)pdT, (ushort_t*)dqkv, (int)B, (int)S, (int)h,
+                scale, keep, salt, (const unsigned long long*)state, dbscr);
+}
+
+// SKY_ATTN_KROWS=0, read at launch like SKY_ATTN_TRV, restores the
+// bwd1s + bwd2 pair; S = 1 always runs it (the dot hand-off needs S >= 2).
+static bool attn_bwd_use_krows(int64_t S) {
+  const char* e = getenv("SKY_ATTN_KROWS");
+  return S >= 2 && !(e && e[0] == '0');
+}
+
 // the bwd1s + bwd2 pair; DBIAS also fills the column-partial scratch
 template <bool DBIAS>
 static void launch_attn_bwd_pair(hipStream_t s, uint64_t qkv, uint64_t dout,
@@ -581,9 +915,14 @@ SKY_EXPORT int sky_attn_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
                             float scale, float keep, uint64_t salt,
                             uint64_t state) {
   if (d != ATT_D || S > ATT_SMAX) return (int)hipErrorInvalidValue;
-  launch_attn_bwd_pair<false>((hipStream_t)stream, qkv, dout, mask, m, lsum,
-                              pdT, dsT, dqkv, B, S, h, scale, keep, salt,
-                              state, nullptr);
+  if (attn_bwd_use_krows(S))
+    launch_attn_bwd_krows<false>((hipStream_t)stream, qkv, dout, mask, m, lsum,
+                                 pdT, dqkv, B, S, h, scale, keep, salt, state,
+                                 nullptr);
+  else
+    launch_attn_bwd_pair<false>((hipStream_t)stream, qkv, dout, mask, m, lsum,
+                                pdT, dsT, dqkv, B, S, h, scale, keep, salt,
+                                state, nullptr);
   LAUNCH_CHECK();
   return 0;
 }
@@ -606,8 +945,12 @@ static int attn_bwd_dbias_impl(uint64_t stream, uint64_t qkv, uint64_t dout,
   if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  launch_attn_bwd_pair<true>(s, qkv, dout, mask, m, lsum, pdT, dsT, dqkv, B, S,
-                             h, scale, keep, salt, state, (float*)scratch);
+  if (attn_bwd_use_krows(S))
+    launch_attn_bwd_krows<true>(s, qkv, dout, mask, m, lsum, pdT, dqkv, B, S, h,
+                                scale, keep, salt, state, (float*)scratch);
+  else
+    launch_attn_bwd_pair<true>(s, qkv, dout, mask, m, lsum, pdT, dsT, dqkv, B,
+                               S, h, scale, keep, salt, state, (float*)scratch);
   const int64_t cols = 3 * h * ATT_D, nslabs = B * ((S + 63) / 64);
   if (job)
     sky_finish_job_set(job, scratch, dbias, 0, 0, nslabs, cols, 1, dbias_dt);

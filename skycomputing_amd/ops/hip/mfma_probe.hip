@@ -7,10 +7,7 @@
 //   B[k][n]: lane l holds n = l%16, k = 8*(l/16) + j
 //   D[i][n]: lane l holds n = l%16, i = 4*(l/16) + r  (r = 0..3)
 
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "attn_common.h"
 
 __global__ __launch_bounds__(64) void mfma_probe_kernel(
     const ushort_t* __restrict__ A, const ushort_t* __restrict__ B,
@@ -38,6 +35,54 @@ SKY_EXPORT int sky_mfma_probe(uint64_t stream, uint64_t A, uint64_t B,
   hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0,
                      (hipStream_t)stream, (const ushort_t*)A,
                      (const ushort_t*)B, (float*)D);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// Chained-MFMA probe: the D tiles of one MFMA as the B operand of the next,
+// as the keys-on-rows attention kernels chain them. D = A(32x32) @ B(32x16)
+// is two stacked D tiles T0 (rows 0..15) and T1; att_pack_dpair makes them a
+// B operand whose slot (lg, j) stands for row (j < 4 ? 0 : 16) + lg*4 + (j & 3)
+// of D, and abf_tr_rows64_2 reads the matching A operand from the row-major
+// [k][64] sw7 image of A2^T (A2 is [16][32], i x k). D2 = A2 @ bf16(D).
+__global__ __launch_bounds__(64) void mfma_chain_probe_kernel(
+    const ushort_t* __restrict__ A, const ushort_t* __restrict__ B,
+    const ushort_t* __restrict__ A2, float* __restrict__ D2) {
+  __shared__ __attribute__((aligned(16))) char img[32 * 128];
+  const int l = threadIdx.x;
+  const int lm = l & 15, lg = l >> 4;
+  // image row k, column i of A2^T (columns 16..63 unused, zeroed)
+  for (int u = l; u < 32 * 64; u += 64) {
+    const int k = u >> 6, i = u & 63;
+    *(ushort_t*)lds_at(img, swz(k * 128 + i * 2, k, 7)) =
+        i < 16 ? A2[i * 32 + k] : (ushort_t)0;
+  }
+  __syncthreads();
+  bf16x8 b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) b[j] = (short)B[(8 * lg + j) * 16 + lm];
+  f32x4 t[2];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    bf16x8 a;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = (short)A[(tt * 16 + lm) * 32 + 8 * lg + j];
+    t[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    t[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, t[tt], 0, 0, 0);
+  }
+  const bf16x8 bd = att_pack_dpair(t[0], t[1]);
+  const bf16x8 a2 = abf_tr_rows64_2(img, 0, lg * 4, 16 + lg * 4, 0, lm);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bd, acc, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) D2[(4 * lg + r) * 16 + lm] = acc[r];
+}
+
+SKY_EXPORT int sky_mfma_chain_probe(uint64_t stream, uint64_t A, uint64_t B,
+                                    uint64_t A2, uint64_t D2) {
+  hipLaunchKernelGGL(mfma_chain_probe_kernel, dim3(1), dim3(64), 0,
+                     (hipStream_t)stream, (const ushort_t*)A,
+                     (const ushort_t*)B, (const ushort_t*)A2, (float*)D2);
   LAUNCH_CHECK();
   return 0;
 }

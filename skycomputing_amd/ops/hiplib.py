@@ -87,6 +87,7 @@ def _register_signatures(lib):
         "sky_hblt_wgrad": [u64, u64, u64, u64, i64, i64, i64, i32],  # strm x dy dw M N K dt
         "sky_hblt_linear_gelu_aux": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i32, i32],  # strm x w bias y aux M N K dt aux_dt
         "sky_mfma_probe": [u64, u64, u64, u64],  # strm A B D
+        "sky_mfma_chain_probe": [u64, u64, u64, u64, u64],  # strm A B A2 D2
         "sky_glds_probe": [u64, u64, u64, i32],
         "sky_probe_bf16_round": [u64, u64],  # strm counts (3 x uint64, device)
         "sky_gemm": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32],
@@ -103,6 +104,8 @@ def _register_signatures(lib):
         #                      strm qkv mask out  m    l    B    S    h    d scale keep salt state
         "sky_attn_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout mask m l pdT dsT dqkv | B S h d scale keep salt state
+        # (default keys-on-rows pair: only fp32 dot [B*h*S] at the head of
+        # pdT is written; SKY_ATTN_KROWS=0 or S = 1: bwd1s + bwd2 fill both)
         "sky_attn_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
         # sky_attn_bwd's arguments + scratch (fp32 [B*ceil(S/64)][3*h*d]),
         # dbias [3*h*d] (column sum of dqkv as stored), dbias dt

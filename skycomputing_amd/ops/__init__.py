@@ -117,8 +117,11 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
     returns [B, S, h*d].
 
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
-    (FusedAttentionFn). Otherwise: strided-view batched GEMMs + fused
-    masked softmax (HIP on GPU, eager on CPU)."""
+    (FusedAttentionFn); 128 < S <= 4096: its chunked form where
+    functions.attn_long_enabled selects it (256 <= S <= 512 by default,
+    SKY_ATTN_LONG=1/0 for all / none), else torch sdpa. Otherwise:
+    strided-view batched GEMMs + fused masked softmax (HIP on GPU, eager on
+    CPU)."""
     from .functions import _split_heads
 
     B, S, three, h, d = qkv.shape
@@ -127,9 +130,14 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
         qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64
         and hiplib.available() and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
     ):
-        from .functions import FlashAttentionFn, FusedAttentionFn
+        from .functions import (
+            FlashAttentionFn, FusedAttentionFn, attn_long_enabled,
+        )
 
-        if S <= 128:
+        # S <= 128: the one-chunk kernels. Above: the chunked keys-on-rows
+        # kernels (ops/hip/attention_long.hip) where SKY_ATTN_LONG or the
+        # measured default selects them, under the same RNG contract.
+        if S <= 128 or attn_long_enabled(S):
             out = FusedAttentionFn.apply(qkv, mask, scale, dropout_p, training)
             return out.reshape(B, S, h * d)
         if S <= 4096 and os.environ.get("SKY_FLASH_ATTN") == "1":
@@ -207,7 +215,8 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
     for hidden [B, S, H], mask [B, 1, 1, S] additive or None.
 
-    GPU, bf16, head dim 64, S <= 128, both biases present and the
+    GPU, bf16, head dim 64, S <= 128 (or S <= 4096 where the long attention
+    kernels are selected, SKY_ATTN_LONG), both biases present and the
     LayerNorm width supported by the three-sum backward: one autograd node
     (AttentionBlockFn) whose backward takes the qkv dbias from the
     attention backward kernels and sums hidden's two gradients inside the
@@ -219,18 +228,21 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     d = H // num_heads
     if (
         hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
-        and S <= 128 and qkv_bias is not None and out_bias is not None
+        and qkv_bias is not None and out_bias is not None
         and hiplib.available()
         and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
         and os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1"
         and os.environ.get("SKY_ATTN_FUSED_BWD") != "1"
     ):
         from .functions import (
-            AttentionBlockFn, attn_block_enabled, ln_dbias_enabled,
-            ln_xsum_width_ok,
+            AttentionBlockFn, attn_block_enabled, attn_long_enabled,
+            ln_dbias_enabled, ln_xsum_width_ok,
         )
 
-        if attn_block_enabled() and ln_dbias_enabled() and ln_xsum_width_ok(H):
+        if (
+            (S <= 128 or attn_long_enabled(S)) and attn_block_enabled()
+            and ln_dbias_enabled() and ln_xsum_width_ok(H)
+        ):
             ap = attn_dropout_p if (training and attn_dropout_p > 0) else 0.0
             hp = hidden_dropout_p if training else 0.0
             return AttentionBlockFn.apply(

@@ -320,9 +320,33 @@ def _attn_bwd_decomposed(qkv, P, Pd, dout, scale, dP_of):
     return dqkv
 
 
+# S above which attention runs the chunked kernels of ops/hip/attention_long.hip
+ATTN_SMAX = 128
+ATTN_LONG_SMAX = 4096
+# SKY_ATTN_LONG unset: the (lo, hi] range of S that takes the long kernels by
+# default: 256 <= S <= 512, the two lengths at which the in-application A/B
+# against sdpa met the bar of ARCHITECTURE section 7 (profiles/r12_notes.md).
+# Outside it nothing was measured in the application and sdpa stays.
+_ATTN_LONG_DEFAULT = (255, 512)
+
+
+def attn_long_enabled(S: int) -> bool:
+    """Whether ops.attention / ops.attention_block run the long-sequence
+    kernels at this S: SKY_ATTN_LONG=1 everywhere in 128 < S <= 4096,
+    SKY_ATTN_LONG=0 nowhere (torch sdpa, as before), unset by measurement."""
+    if not ATTN_SMAX < S <= ATTN_LONG_SMAX:
+        return False
+    e = os.environ.get("SKY_ATTN_LONG")
+    if e in ("0", "1"):
+        return e == "1"
+    return (_ATTN_LONG_DEFAULT is not None
+            and _ATTN_LONG_DEFAULT[0] < S <= _ATTN_LONG_DEFAULT[1])
+
+
 def _attn_fwd(qkv, mask, scale, keep):
-    """sky_attn_fwd on a contiguous packed qkv [B, S, 3, h, 64]; draws the
-    dropout salt when keep < 1. Returns (out [B, S, h, d], m, lsum, salt)."""
+    """sky_attn_fwd (S <= 128) or sky_attn_long_fwd on a contiguous packed
+    qkv [B, S, 3, h, 64]; draws the dropout salt when keep < 1. Returns
+    (out [B, S, h, d], m, lsum, salt)."""
     lib = hiplib.require()
     B, S, _, h, d = qkv.shape
     out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
@@ -330,14 +354,27 @@ def _attn_fwd(qkv, mask, scale, keep):
     lsum = torch.empty_like(m)
     salt = _next_seed() if keep < 1.0 else 0
     state = rng_state()
+    name = "sky_attn_long_fwd" if S > ATTN_SMAX else "sky_attn_fwd"
     check(
-        lib.sky_attn_fwd(
+        getattr(lib, name)(
             _stream(), ptr(qkv), ptr(mask), ptr(out), ptr(m), ptr(lsum),
             B, S, h, d, scale, keep, salt, state.data_ptr(),
         ),
-        "sky_attn_fwd",
+        name,
     )
     return out, m, lsum, salt
+
+
+def _attn_long_bwd_args(qkv, dout, out, mask, m, lsum, dot, dqkv, scale,
+                        keep, salt):
+    """The arguments the three sky_attn_long_bwd* entry points share. out is
+    the forward's output (the dQ kernel takes the row dot from dO * O); dot,
+    fp32 [B*h*S] from the caller, is the only scratch: the dQ kernel hands
+    it to the dK/dV kernel."""
+    B, S, _, h, d = qkv.shape
+    return (_stream(), ptr(qkv), ptr(dout), ptr(out), ptr(mask), ptr(m),
+            ptr(lsum), ptr(dot), ptr(dqkv), B, S, h, d, scale, keep, salt,
+            rng_state().data_ptr())
 
 
 def _attn_bwd_scratch(qkv):
@@ -375,21 +412,36 @@ class FusedAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, mask, scale, dropout_p, training):
         B, S, three, h, d = qkv.shape
-        assert three == 3 and d == 64 and S <= 128
+        assert three == 3 and d == 64 and S <= ATTN_LONG_SMAX
         qkv = qkv.contiguous()
         mask = mask.contiguous() if mask is not None else None
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
         out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep)
-        ctx.save_for_backward(qkv, mask, m, lsum)
+        # the long backward takes its row dots from dO * O
+        extra = (out,) if S > ATTN_SMAX else ()
+        ctx.save_for_backward(qkv, mask, m, lsum, *extra)
         ctx.scale, ctx.keep, ctx.salt = scale, keep, salt
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = hiplib.require()
-        qkv, mask, m, lsum = ctx.saved_tensors
+        qkv, mask, m, lsum, *extra = ctx.saved_tensors
         B, S, _, h, d = qkv.shape
         dev = qkv.device
+        if S > ATTN_SMAX:
+            # dQ + dot, then dK/dV (ops/hip/attention_long.hip); the env
+            # switches below select among the S <= 128 kernels only
+            dout = dout.contiguous()
+            dqkv = torch.empty_like(qkv)
+            dot = torch.empty(B * h * S, dtype=torch.float32, device=dev)
+            check(
+                lib.sky_attn_long_bwd(*_attn_long_bwd_args(
+                    qkv, dout, extra[0], mask, m, lsum, dot, dqkv, ctx.scale,
+                    ctx.keep, ctx.salt)),
+                "sky_attn_long_bwd",
+            )
+            return dqkv, None, None, None, None
         if os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1":
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)
@@ -898,15 +950,15 @@ class AttentionBlockFn(torch.autograd.Function):
         one plus its post-reduction kernel, and
       * fold autograd's add of hidden's two gradients (residual branch and
         qkv linear) into the qkv dgrad GEMM (beta = 1 on dres).
-    bf16, d = 64, S <= 128 only (the fused attention kernels' domain);
-    mask [B, 1, 1, S] additive or None."""
+    bf16, d = 64, S <= 4096 only (the fused attention kernels' domain; the
+    long kernels above S = 128); mask [B, 1, 1, S] additive or None."""
 
     @staticmethod
     def forward(ctx, hidden, wqkv, bqkv, mask, num_heads, attn_p, wo, bo,
                 ln_w, ln_b, eps, hidden_p):
         B, S, H = hidden.shape
         d = H // num_heads
-        assert d == 64 and S <= 128 and hidden.dtype == torch.bfloat16
+        assert d == 64 and S <= ATTN_LONG_SMAX and hidden.dtype == torch.bfloat16
         hidden = hidden.contiguous()
         x2 = hidden.view(-1, H)
         qkv = _linear_fwd(x2, wqkv, bqkv).view(B, S, 3, num_heads, d)
@@ -942,22 +994,36 @@ class AttentionBlockFn(torch.autograd.Function):
         dwo = _wgrad_plain(dh2, c2, wo)
         dqkv = torch.empty_like(qkv)
         dbqkv = torch.empty(3 * H, dtype=wqkv.dtype, device=qkv.device)
-        pdT, dsT = _attn_bwd_scratch(qkv)
+        # the S <= 128 scratch first, then the slabs: the allocation order
+        # this node has always had
+        if S > ATTN_SMAX:
+            scratch = (torch.empty(B * nh * S, dtype=torch.float32, device=qkv.device),)
+        else:
+            scratch = _attn_bwd_scratch(qkv)
         # column partials of dqkv, one slab per (batch, 64-query block);
         # the kernels write every element, so no memset
         slabs = torch.empty(B * ((S + 63) // 64) * 3 * H, dtype=torch.float32,
                             device=qkv.device)
-        args = (_stream(), ptr(qkv), ptr(dctx), ptr(mask), ptr(m), ptr(lsum),
-                ptr(pdT), ptr(dsT), ptr(dqkv), B, S, nh, d, ctx.scale,
-                ctx.akeep, ctx.asalt, rng_state().data_ptr(), ptr(slabs),
-                ptr(dbqkv), _dt(dbqkv))
+        if S > ATTN_SMAX:
+            # c2 is the attention output the forward saved for dWo;
+            # scratch is dot, fp32 [B*h*S]
+            entry = "sky_attn_long_bwd_dbias"
+            args = _attn_long_bwd_args(qkv, dctx, c2, mask, m, lsum, scratch[0],
+                                       dqkv, ctx.scale, ctx.akeep, ctx.asalt)
+        else:
+            entry = "sky_attn_bwd_dbias"
+            pdT, dsT = scratch
+            args = (_stream(), ptr(qkv), ptr(dctx), ptr(mask), ptr(m),
+                    ptr(lsum), ptr(pdT), ptr(dsT), ptr(dqkv), B, S, nh, d,
+                    ctx.scale, ctx.akeep, ctx.asalt, rng_state().data_ptr())
+        args += (ptr(slabs), ptr(dbqkv), _dt(dbqkv))
         if pending is not None:
-            check(lib.sky_attn_bwd_dbias_parts(*args, pending.slot()),
-                  "sky_attn_bwd_dbias_parts")
+            check(getattr(lib, entry + "_parts")(*args, pending.slot()),
+                  entry + "_parts")
             pending.took(slabs)
             pending.run()
         else:
-            check(lib.sky_attn_bwd_dbias(*args), "sky_attn_bwd_dbias")
+            check(getattr(lib, entry)(*args), entry)
         dqkv2 = dqkv.view(-1, 3 * H)
         dwqkv = _wgrad_plain(dqkv2, x2, wqkv)
         # d hidden = dres + dqkv @ Wqkv, accumulated by the GEMM. Without

@@ -1,0 +1,640 @@
+// Attention for 128 < S <= 4096 (d = 64, bf16): the keys-on-rows kernels of
+// attention.hip / attention_bwd.hip turned into flash kernels. The S <= 128
+// kernels hold a whole row of scores in registers; here the other side of
+// each product arrives in chunks of 128 tokens, staged into the same two
+// [128][64] sw7 images, and what a lane carries from chunk to chunk is per
+// lane:
+//   * forward: with keys on the MFMA rows a lane owns ONE query in both
+//     S^T = K Q^T and O^T = V^T Pd^T, so the online-softmax state (m, l) is
+//     two lane scalars and the rescale oacc *= exp(m - m_new) touches only
+//     the lane's own registers: no shuffle, no LDS;
+//   * dQ: the row dot cannot wait for the last chunk, so it is taken up
+//     front as sum_j dO[q,j] * O[q,j] (equal to sum_k dP * P, dropout
+//     included), the diagonal of one 16 x 16 MFMA tile O dO^T; P comes from
+//     the saved m and 1/l, dS^T overwrites it and feeds dQ^T += K^T dS^T;
+//   * dK/dV: a wave owns 16 keys, dK^T and dV^T stay in registers across
+//     the walk over the queries.
+// No S x S tensor and no scratch beyond dot [B*h*S] fp32 exists anywhere.
+// Dropout: att_drop_hash_c64 + att_drop_keep (attn_common.h), regenerated
+// in both backward kernels from (salt, state).
+
+#include "attn_common.h"
+
+#define ATL_SMAX 4096
+
+// Every kernel of this file is compiled without the packed fp32 VALU ops
+// (v_pk_mul_f32, v_pk_fma_f32, v_pk_add_f32). With them the compiler packs
+// the score loops of the forward into register pairs and the kernel goes
+// from 102 VGPRs to 128 with some 3300 spilled registers; zero scratch is a
+// requirement here, so the feature is switched off in the source and not
+// left to a build flag.
+#if defined(__HIP_DEVICE_COMPILE__)  // the host pass does not know the feature
+#define ATL_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define ATL_NO_PK_F32
+#endif
+#define ATL_KERNEL ATL_NO_PK_F32 __global__ __launch_bounds__(256, 4)
+
+// lm / lg made opaque once per chunk. Inside a chunk loop every LDS address
+// is loop-invariant; the compiler hoists them all out of the loop and the
+// ~50 registers that hold them spill. Addresses built from the opaque copies
+// are recomputed per chunk, which is what the S <= 128 kernels pay once.
+// Global indices (hashes, masks, rows) keep the plain lm / lg.
+DEV void atl_chunk_lanes(int& lmc, int& lgc, int lm, int lg) {
+  lmc = lm;
+  lgc = lg;
+  asm volatile("" : "+v"(lmc), "+v"(lgc));
+}
+
+// two adjacent transposed score tiles (2*kp, 2*kp + 1) of a [128][64] sw7
+// image: att_score_tile_t restricted to one pair, so that only the pair is
+// live while its dS goes into the next MFMA. Tiles >= nt keep their zeros.
+DEV void atl_score_pair_t(f32x4 (&acc)[2], const bf16x8 (&b)[2], char* lds,
+                          int off, int kp, int nt, int lm, int lg) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (2 * kp + t >= nt) continue;
+    const int tok = (2 * kp + t) * 16 + lm;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 at = *(const bf16x8*)lds_at(
+          lds, swz(off + tok * 128 + (ks * 32 + lg * 8) * 2, tok, 7));
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at, b[ks], acc[t], 0, 0, 0);
+    }
+  }
+}
+
+// the lane's hashes for chunk kc: z[r][half] covers keys
+// kc*128 + half*64 + (mt & 3)*16 + lg*4 + r, read as att_drop_keep(z[r], mt)
+DEV void atl_drop_hash_chunk(uint64_t (&z)[4][2], uint64_t seed, int bh, int S,
+                             int q, int lg, int kc) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    z[r][0] = att_drop_hash_c64(seed, bh, S, q, lg * 4 + r, kc * 2);
+    z[r][1] = att_drop_hash_c64(seed, bh, S, q, lg * 4 + r, kc * 2 + 1);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Forward. One block per (b, h, 64-query block), a wave owns 16 queries
+// (fragments from global). LDS: K chunk @0, V chunk @16K, the chunk's key
+// mask fp32 @32K: 33 KB, four blocks per CU, single-buffered: co-resident
+// blocks cover each other's load phase.
+#define ATL_K_OFF KR_IMG0_OFF
+#define ATL_V_OFF KR_IMG1_OFF
+#define ATL_MASK_OFF KR_AUX_OFF
+#define ATL_FWD_LDS (KR_AUX_OFF + 512)
+
+template <bool HAS_MASK>
+ATL_KERNEL void attn_fwd_long_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
+    ushort_t* __restrict__ out, float* __restrict__ m_io,
+    float* __restrict__ l_io, int B, int S, int h, float scale, float keep,
+    uint64_t salt, const unsigned long long* __restrict__ state) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 63) / 64;
+  const int bh = blockIdx.x / QB;
+  const int qb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int NCH = (S + 127) / 128;
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  float* mk = (float*)lds_at(lds, ATL_MASK_OFF);
+
+  const int qtok_base = qb * 64 + w * 16;
+  const bool active = qtok_base < S;  // wave-uniform
+  const int q = qtok_base + lm;       // this lane's query
+  const int qc = q < S ? q : S - 1;
+  bf16x8 bq[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+    bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+
+  // Chunk 0 always holds key 0 and additive masks are finite (-10000), so m
+  // is a real score after chunk 0. Before it, m = -3e38 gives alpha =
+  // exp(-3e38 - m_new) = 0 against l = 0 and O = 0; later, a jump of m by
+  // 1e4 (a chunk of masked keys followed by a visible one) gives alpha = 0
+  // as well, which is the correct weight of the terms so far.
+  float m = -3.0e38f, lsum = 0.f;
+  f32x4 oacc[4];
+  att_zero(oacc);
+
+#pragma clang loop unroll(disable)
+  for (int kc = 0; kc < NCH; ++kc) {
+    const int k0 = kc * 128;
+    const int nk = S - k0 < 128 ? S - k0 : 128;
+    const int NT = (nk + 15) / 16;
+    const int NP = (nk + 31) / 32;  // key-tile pairs = PV contraction steps
+    if (kc) __syncthreads();        // every wave is done with the last chunk
+    // whole tile pairs are staged; tokens >= S re-read token S-1, finite
+    // values that the -3e38 mask (scores) and the zero P (PV) null
+    att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
+    att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
+    att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (!active) continue;
+    int lmc, lgc;
+    atl_chunk_lanes(lmc, lgc, lm, lg);
+
+    f32x4 sacc[8];
+    att_zero(sacc);
+    att_score_tile_t(sacc, bq, lds, ATL_K_OFF, NT, lmc, lgc);
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+      const f32x4 mv = att_mask_keys4(mk, mt, lgc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float zz = sacc[mt][r] * scale + mv[r];
+        sacc[mt][r] = zz;
+        mx = fmaxf(mx, zz);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m, mx);
+    const float alpha = __expf(m - m_new);
+    m = m_new;
+    uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    if (keep < 1.f) atl_drop_hash_chunk(z, seed, bh, S, q, lg, kc);
+    // unnormalised p (the sum takes it before dropout), dropped in place;
+    // keys >= S come out as exact zeros
+    float sm = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      if (mt >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float p = __expf(sacc[mt][r] - m_new);
+        sm += p;
+        if (keep < 1.f) p = att_drop_keep(z[r], mt, keep16) ? p * inv_keep : 0.f;
+        sacc[mt][r] = p;
+      }
+    }
+    sm += __shfl_xor(sm, 16, 64);
+    sm += __shfl_xor(sm, 32, 64);
+    lsum = lsum * alpha + sm;
+    // the O^T column lm is this lane's query: the rescale is lane-local
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) oacc[ct] *= alpha;
+    // O^T += V^T Pd^T: B = the score registers, A = V^T by tr16
+#pragma unroll
+    for (int kp = 0; kp < 4; ++kp) {
+      if (kp >= NP) continue;
+      const bf16x8 bp = att_pack_dpair(sacc[2 * kp], sacc[2 * kp + 1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 av = abf_tr_rows64_2(lds, ATL_V_OFF, kp * 32 + lgc * 4,
+                                          kp * 32 + 16 + lgc * 4, ct * 4, lmc);
+        oacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oacc[ct], 0, 0, 0);
+      }
+    }
+  }
+  if (!active) return;
+  const float inv = 1.f / lsum;
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) oacc[ct] *= inv;
+  if (lg == 0 && q < S) {
+    m_io[(size_t)bh * S + q] = m;
+    l_io[(size_t)bh * S + q] = lsum;
+  }
+  ushort_t* obase = out + ((size_t)b * S * h + hh) * ATT_D;
+  att_store_cols16(obase, h * ATT_D, oacc, qtok_base, S, lm, lg);
+}
+
+// ---------------------------------------------------------------------------
+// Backward dQ. One block per (b, h, 64-query block); K and V come in chunks
+// as in the forward. Per pair of key tiles: S^T and dPd^T, P from the saved
+// statistics, dS^T over the scores, dQ^T += K^T dS^T; only the pair is live.
+// Writes dot[bh*S + q] for the dK/dV kernel; with DBIAS the block's 64 dQ
+// column sums go to slab b*QB + qb. LDS as the forward + DBIAS sums @32.5K.
+#define ATL_SUM_OFF (KR_AUX_OFF + 512)
+#define ATL_DQ_LDS (KR_AUX_OFF + 512 + 1024)
+
+template <bool HAS_MASK, bool DBIAS>
+ATL_KERNEL void attn_bwd_dq_long_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
+    const ushort_t* __restrict__ out, const ushort_t* __restrict__ mask,
+    const float* __restrict__ m_io, const float* __restrict__ l_io,
+    float* __restrict__ dot_out, ushort_t* __restrict__ dqkv, int B, int S,
+    int h, float scale, float keep, uint64_t salt,
+    const unsigned long long* __restrict__ state, float* __restrict__ dbscr) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 63) / 64;
+  const int bh = blockIdx.x / QB;
+  const int qb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int dots = h * ATT_D;
+  const int NCH = (S + 127) / 128;
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D;
+  const ushort_t* obase = out + ((size_t)b * S * h + hh) * ATT_D;
+  float* mk = (float*)lds_at(lds, ATL_MASK_OFF);
+
+  const int qtok_base = qb * 64 + w * 16;
+  const bool active = qtok_base < S;
+  const int q = qtok_base + lm;  // this lane's query
+  const int qc = q < S ? q : S - 1;
+
+  bf16x8 bq[2], bdo[2];
+  // dot[q] = sum_j dO[q,j] * O[q,j] as the diagonal of the wave's 16 x 16
+  // tile O dO^T, from the same MFMA and in the same order over j as
+  // dPd^T = V dO^T below. A VALU sum of the 64 products differs from the
+  // MFMA's in the last bits; where one key holds all of a row's weight
+  // (O = that key's V row) dP - dot must cancel exactly, and it does only if
+  // both come out of the same arithmetic.
+  f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+    bdo[ks] = *(const bf16x8*)(dobase + (size_t)qc * dots + ks * 32 + lg * 8);
+    const bf16x8 ao = *(const bf16x8*)(obase + (size_t)qc * dots + ks * 32 + lg * 8);
+    dd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ao, bdo[ks], dd, 0, 0, 0);
+  }
+  // element (lm, lm) is register lm & 3 of the lane (lg = lm >> 2, lm)
+  const float dsel = (lm & 2) ? ((lm & 1) ? dd[3] : dd[2]) : ((lm & 1) ? dd[1] : dd[0]);
+  const float dot = __shfl(dsel, ((lm >> 2) << 4) | lm, 64);
+  if (active && lg == 0 && q < S) dot_out[(size_t)bh * S + q] = dot;
+  const float mrow = m_io[(size_t)bh * S + qc];
+  const float lrow = 1.f / l_io[(size_t)bh * S + qc];
+
+  f32x4 qacc[4];
+  att_zero(qacc);
+#pragma clang loop unroll(disable)
+  for (int kc = 0; kc < NCH; ++kc) {
+    const int k0 = kc * 128;
+    const int nk = S - k0 < 128 ? S - k0 : 128;
+    const int NT = (nk + 15) / 16;
+    const int NP = (nk + 31) / 32;
+    if (kc) __syncthreads();
+    att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
+    att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
+    att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (!active) continue;
+    int lmc, lgc;
+    atl_chunk_lanes(lmc, lgc, lm, lg);
+
+    uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    if (keep < 1.f) atl_drop_hash_chunk(z, seed, bh, S, q, lg, kc);
+#pragma unroll
+    for (int kp = 0; kp < 4; ++kp) {
+      if (kp >= NP) continue;
+      f32x4 s2[2], d2[2];
+      atl_score_pair_t(s2, bq, lds, ATL_K_OFF, kp, NT, lmc, lgc);   // K Q^T
+      atl_score_pair_t(d2, bdo, lds, ATL_V_OFF, kp, NT, lmc, lgc);  // V dO^T
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int mt = 2 * kp + t;
+        if (mt >= NT) continue;  // s2[t] stays zero: a null dS tile
+        const f32x4 mv = att_mask_keys4(mk, mt, lgc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0 + mt * 16 + lg * 4 + r;
+          const float p = att_prob(s2[t][r], scale, mv[r], mrow, lrow,
+                                   q < S && key < S);
+          float dp = d2[t][r];
+          if (keep < 1.f)
+            dp = att_drop_keep(z[r], mt, keep16) ? dp * inv_keep : 0.f;
+          s2[t][r] = scale * p * (dp - dot);
+        }
+      }
+      const bf16x8 bds = att_pack_dpair(s2[0], s2[1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 ak = abf_tr_rows64_2(lds, ATL_K_OFF, kp * 32 + lgc * 4,
+                                          kp * 32 + 16 + lgc * 4, ct * 4, lmc);
+        qacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, bds, qacc[ct], 0, 0, 0);
+      }
+    }
+  }
+  float cs = 0.f;
+  if (active) {
+    ushort_t* dq = dqkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+    att_store_cols16(dq, ts, qacc, qtok_base, S, lm, lg);
+    if constexpr (DBIAS) cs = att_colsum_cols16(qacc, qtok_base, S, lm);
+  }
+  if constexpr (DBIAS) {
+    // inactive waves contribute their zeros and must reach the barrier too
+    float* wsum = (float*)lds_at(lds, ATL_SUM_OFF);  // [4 waves][64 cols]
+    wsum[w * 64 + att_colsum_cols16_col(lm, lg)] = cs;
+    __syncthreads();
+    if (tid < 64)
+      dbscr[((size_t)b * QB + qb) * ts + (size_t)hh * ATT_D + tid] =
+          (wsum[tid] + wsum[64 + tid]) + (wsum[128 + tid] + wsum[192 + tid]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Backward dK/dV. One block per (b, h, 64-key block), launched after the dQ
+// kernel (it reads dot). A wave owns 16 keys, K and V fragments from global;
+// dK^T and dV^T stay in registers while the queries go by in chunks of 128:
+// Q and dO images, m | 1/l | dot and the chunk's keep bits in LDS, and inside
+// a chunk pairs of 16-row tiles as in attn_bwd_dkv_krows_kernel. With DBIAS
+// the dK and dV column sums go to slab b*QB + kb.
+// LDS: Q chunk @0, dO chunk @16K, m | 1/l | dot fp32 [128] each @32K, keep
+// bits (att_drop_bits_lds_long) @33.5K, DBIAS sums [4][dK 64 | dV 64] @35.5K.
+#define ATL_Q_OFF KR_IMG0_OFF
+#define ATL_DO_OFF KR_IMG1_OFF
+#define ATL_STAT_OFF KR_AUX_OFF
+#define ATL_BITS_OFF (KR_AUX_OFF + 1536)
+#define ATL_SUM2_OFF (KR_AUX_OFF + 1536 + 2048)
+#define ATL_DKV_LDS (KR_AUX_OFF + 1536 + 2048 + 2048)
+
+template <bool HAS_MASK, bool DBIAS>
+ATL_KERNEL void attn_bwd_dkv_long_kernel(
+    const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
+    const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
+    const float* __restrict__ l_io, const float* __restrict__ dot_in,
+    ushort_t* __restrict__ dqkv, int B, int S, int h, float scale, float keep,
+    uint64_t salt, const unsigned long long* __restrict__ state,
+    float* __restrict__ dbscr) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x;
+  const int l = tid & 63;
+  const int w = tid >> 6;
+  const int lm = l & 15;
+  const int lg = l >> 4;
+  const int QB = (S + 63) / 64;
+  const int bh = blockIdx.x / QB;
+  const int kb = blockIdx.x % QB;
+  const int b = bh / h;
+  const int hh = bh % h;
+  const int ts = 3 * h * ATT_D;
+  const int dots = h * ATT_D;
+  const int NCH = (S + 127) / 128;
+  const uint64_t seed = rng_seed(salt, state);
+  const float inv_keep = 1.f / keep;
+  const unsigned keep16 = keep_to_16(keep);
+
+  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D;
+  const ushort_t* kbase = qbase + (size_t)h * ATT_D;
+  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D;
+  const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D;
+  float* st = (float*)lds_at(lds, ATL_STAT_OFF);
+  unsigned char* bits = (unsigned char*)lds_at(lds, ATL_BITS_OFF);
+
+  const int ktok_base = kb * 64 + w * 16;
+  const bool active = ktok_base < S;
+  const int key = ktok_base + lm;  // this lane's key
+  const int kc = key < S ? key : S - 1;
+
+  bf16x8 bk[2], bv[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bk[ks] = *(const bf16x8*)(kbase + (size_t)kc * ts + ks * 32 + lg * 8);
+    bv[ks] = *(const bf16x8*)(vbase + (size_t)kc * ts + ks * 32 + lg * 8);
+  }
+  float mv = 0.f;
+  if (HAS_MASK && key < S) mv = bf16_to_f32(mask[(size_t)b * S + key]);
+  if (key >= S) mv = -3.0e38f;
+
+  f32x4 kacc[4], vacc[4];
+  att_zero(kacc);
+  att_zero(vacc);
+#pragma clang loop unroll(disable)
+  for (int qch = 0; qch < NCH; ++qch) {
+    const int q0 = qch * 128;
+    const int nq = S - q0 < 128 ? S - q0 : 128;
+    const int NT = (nq + 15) / 16;
+    const int NP = (nq + 31) / 32;
+    if (qch) __syncthreads();  // the one barrier before LDS is reused
+    att_glds_rows(qbase, ts, q0, NP * 32, true, S, lds, ATL_Q_OFF, tid);
+    att_glds_rows(dobase, dots, q0, NP * 32, true, S, lds, ATL_DO_OFF, tid);
+    // rows >= S: 1/l = 0 and a false valid flag null P, dot = 0 keeps dS finite
+    if (tid < ATT_SMAX) {
+      const int row = q0 + tid;
+      const bool live = row < S;
+      st[tid] = live ? m_io[(size_t)bh * S + row] : 0.f;
+      st[128 + tid] = live ? 1.f / l_io[(size_t)bh * S + row] : 0.f;
+      st[256 + tid] = live ? dot_in[(size_t)bh * S + row] : 0.f;
+    }
+    if (keep < 1.f)
+      att_drop_bits_lds_long(bits, seed, bh, S, kb, q0, NP * 32, keep16, tid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (!active) continue;
+    int lmc, lgc;
+    atl_chunk_lanes(lmc, lgc, lm, lg);
+
+#pragma unroll
+    for (int qp = 0; qp < 4; ++qp) {
+      if (qp >= NP) continue;
+      f32x4 pd[2], ds[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int qt = 2 * qp + t;
+        pd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        ds[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (qt >= NT) continue;
+        const int qrow = qt * 16 + lmc;  // < NP*32: a staged (clamped) row
+        f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, d4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const bf16x8 aq = *(const bf16x8*)lds_at(
+              lds, swz(ATL_Q_OFF + qrow * 128 + (ks * 32 + lgc * 8) * 2, qrow, 7));
+          const bf16x8 ado = *(const bf16x8*)lds_at(
+              lds, swz(ATL_DO_OFF + qrow * 128 + (ks * 32 + lgc * 8) * 2, qrow, 7));
+          s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, bk[ks], s4, 0, 0, 0);
+          d4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado, bv[ks], d4, 0, 0, 0);
+        }
+        const f32x4 m4 = *(const f32x4*)(st + qt * 16 + lgc * 4);
+        const f32x4 il4 = *(const f32x4*)(st + 128 + qt * 16 + lgc * 4);
+        const f32x4 dot4 = *(const f32x4*)(st + 256 + qt * 16 + lgc * 4);
+        unsigned kbits = 0xFFFFFFFFu;
+        if (keep < 1.f)
+          kbits = *(const unsigned*)(bits + ((qt * 4 + lgc) * 16 + lmc) * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qq = q0 + qt * 16 + lg * 4 + r;
+          const float p = att_prob(s4[r], scale, mv, m4[r], il4[r],
+                                   qq < S && key < S);
+          const bool kbit = (kbits >> (8 * r + w)) & 1u;
+          float pdv = p, dp = d4[r];
+          if (keep < 1.f) {
+            pdv = kbit ? p * inv_keep : 0.f;
+            dp = kbit ? dp * inv_keep : 0.f;
+          }
+          pd[t][r] = pdv;
+          ds[t][r] = scale * p * (dp - dot4[r]);
+        }
+      }
+      const bf16x8 bpd = att_pack_dpair(pd[0], pd[1]);
+      const bf16x8 bds = att_pack_dpair(ds[0], ds[1]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const bf16x8 adot = abf_tr_rows64_2(lds, ATL_DO_OFF, qp * 32 + lgc * 4,
+                                            qp * 32 + 16 + lgc * 4, ct * 4, lmc);
+        vacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adot, bpd, vacc[ct], 0, 0, 0);
+        const bf16x8 aqt = abf_tr_rows64_2(lds, ATL_Q_OFF, qp * 32 + lgc * 4,
+                                           qp * 32 + 16 + lgc * 4, ct * 4, lmc);
+        kacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aqt, bds, kacc[ct], 0, 0, 0);
+      }
+    }
+  }
+  float ck = 0.f, cv = 0.f;
+  if (active) {
+    ushort_t* dk = dqkv + (size_t)b * S * ts + (size_t)(h + hh) * ATT_D;
+    ushort_t* dv = dqkv + (size_t)b * S * ts + (size_t)(2 * h + hh) * ATT_D;
+    att_store_cols16(dk, ts, kacc, ktok_base, S, lm, lg);
+    att_store_cols16(dv, ts, vacc, ktok_base, S, lm, lg);
+    if constexpr (DBIAS) {
+      ck = att_colsum_cols16(kacc, ktok_base, S, lm);
+      cv = att_colsum_cols16(vacc, ktok_base, S, lm);
+    }
+  }
+  if constexpr (DBIAS) {
+    float* wsum = (float*)lds_at(lds, ATL_SUM2_OFF);  // [4][dK 64 | dV 64]
+    const int c = att_colsum_cols16_col(lm, lg);
+    wsum[w * 128 + c] = ck;
+    wsum[w * 128 + 64 + c] = cv;
+    __syncthreads();
+    if (tid < 128) {
+      // tid < 64: dK column tid; otherwise dV column tid - 64
+      const size_t col = (size_t)((tid < 64 ? h : 2 * h) + hh) * ATT_D + (tid & 63);
+      dbscr[((size_t)b * QB + kb) * ts + col] =
+          (wsum[tid] + wsum[128 + tid]) + (wsum[256 + tid] + wsum[384 + tid]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Entry points: d = 64 and 128 < S <= 4096 only (S <= 128 belongs to
+// sky_attn_fwd / sky_attn_bwd*).
+static bool atl_shape_ok(int64_t S, int64_t d) {
+  return d == ATT_D && S > ATT_SMAX && S <= ATL_SMAX;
+}
+
+SKY_EXPORT int sky_attn_long_fwd(uint64_t stream, uint64_t qkv, uint64_t mask,
+                                 uint64_t out, uint64_t m, uint64_t lsum,
+                                 int64_t B, int64_t S, int64_t h, int64_t d,
+                                 float scale, float keep, uint64_t salt,
+                                 uint64_t state) {
+  if (!atl_shape_ok(S, d)) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  ATT_LAUNCH_HM(mask != 0, (attn_fwd_long_kernel<HM>), grid, ATL_FWD_LDS,
+                (hipStream_t)stream, (const ushort_t*)qkv,
+                (const ushort_t*)mask, (ushort_t*)out, (float*)m, (float*)lsum,
+                (int)B, (int)S, (int)h, scale, keep, salt,
+                (const unsigned long long*)state);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// dQ + dot, then dK/dV; DBIAS also fills the column-partial slabs
+template <bool DBIAS>
+static void launch_attn_long_bwd(hipStream_t s, uint64_t qkv, uint64_t dout,
+                                 uint64_t out, uint64_t mask, uint64_t m,
+                                 uint64_t lsum, uint64_t dot, uint64_t dqkv,
+                                 int64_t B, int64_t S, int64_t h, float scale,
+                                 float keep, uint64_t salt, uint64_t state,
+                                 float* dbscr) {
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  ATT_LAUNCH_HM(mask != 0, (attn_bwd_dq_long_kernel<HM, DBIAS>), grid,
+                ATL_DQ_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)out, (const ushort_t*)mask, (const float*)m,
+                (const float*)lsum, (float*)dot, (ushort_t*)dqkv, (int)B,
+                (int)S, (int)h, scale, keep, salt,
+                (const unsigned long long*)state, dbscr);
+  ATT_LAUNCH_HM(mask != 0, (attn_bwd_dkv_long_kernel<HM, DBIAS>), grid,
+                ATL_DKV_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
+                (const float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h,
+                scale, keep, salt, (const unsigned long long*)state, dbscr);
+}
+
+// out: the forward's output [B,S,h,d]; dot: fp32 [B*h*S], written by the
+// dQ kernel and read by the dK/dV kernel.
+SKY_EXPORT int sky_attn_long_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
+                                 uint64_t out, uint64_t mask, uint64_t m,
+                                 uint64_t lsum, uint64_t dot, uint64_t dqkv,
+                                 int64_t B, int64_t S, int64_t h, int64_t d,
+                                 float scale, float keep, uint64_t salt,
+                                 uint64_t state) {
+  if (!atl_shape_ok(S, d) || out == 0 || dot == 0)
+    return (int)hipErrorInvalidValue;
+  launch_attn_long_bwd<false>((hipStream_t)stream, qkv, dout, out, mask, m,
+                              lsum, dot, dqkv, B, S, h, scale, keep, salt,
+                              state, nullptr);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// sky_attn_long_bwd that also returns dbias[3*h*64], the column sums of dqkv
+// as stored; scratch: fp32 [B * ceil(S/64)][3*h*64], every element written.
+// job == nullptr: the slab reduction runs here; otherwise it is left
+// pending in *job (as attn_bwd_dbias_impl, attention_bwd.hip).
+static int attn_long_bwd_dbias_impl(uint64_t stream, uint64_t qkv,
+                                    uint64_t dout, uint64_t out, uint64_t mask,
+                                    uint64_t m, uint64_t lsum, uint64_t dot,
+                                    uint64_t dqkv, int64_t B, int64_t S,
+                                    int64_t h, int64_t d, float scale,
+                                    float keep, uint64_t salt, uint64_t state,
+                                    uint64_t scratch, uint64_t dbias,
+                                    int dbias_dt, SkyFinishJob* job) {
+  if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || scratch == 0 || dbias == 0)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  launch_attn_long_bwd<true>(s, qkv, dout, out, mask, m, lsum, dot, dqkv, B, S,
+                             h, scale, keep, salt, state, (float*)scratch);
+  const int64_t cols = 3 * h * ATT_D, nslabs = B * ((S + 63) / 64);
+  if (job)
+    sky_finish_job_set(job, scratch, dbias, 0, 0, nslabs, cols, 1, dbias_dt);
+  else
+    sky_launch_colsum_final(s, (const float*)scratch, (void*)dbias, cols,
+                            nslabs, dbias_dt);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_long_bwd_dbias(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t mask,
+    uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt) {
+  return attn_long_bwd_dbias_impl(stream, qkv, dout, out, mask, m, lsum, dot,
+                                  dqkv, B, S, h, d, scale, keep, salt, state,
+                                  scratch, dbias, dbias_dt, nullptr);
+}
+
+SKY_EXPORT int sky_attn_long_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t mask,
+    uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt,
+    uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_long_bwd_dbias_impl(stream, qkv, dout, out, mask, m, lsum, dot,
+                                  dqkv, B, S, h, d, scale, keep, salt, state,
+                                  scratch, dbias, dbias_dt, (SkyFinishJob*)job);
+}

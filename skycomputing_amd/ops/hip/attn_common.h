@@ -182,6 +182,17 @@ DEV void att_mask_keys_lds(float* mk, bool has_mask,
 DEV f32x4 att_mask_keys4(const float* mk, int mt, int lg) {
   return *(const f32x4*)(mk + mt * 16 + lg * 4);
 }
+// the same image for the 128-key chunk that starts at key k0 (S > 128)
+DEV void att_mask_keys_lds_at(float* mk, bool has_mask,
+                              const ushort_t* __restrict__ mask, int b, int S,
+                              int k0, int tid) {
+  if (tid < ATT_SMAX) {
+    const int key = k0 + tid;
+    float mv = 0.f;
+    if (has_mask && key < S) mv = bf16_to_f32(mask[(size_t)b * S + key]);
+    mk[tid] = (key < S) ? mv : -3.0e38f;
+  }
+}
 
 // stage nrows rows of a [tok][64] bf16 row image (token stride tstride,
 // first token tok0) to LDS offset off via global_load_lds. The XOR swizzle
@@ -219,6 +230,17 @@ DEV uint64_t att_drop_hash_half(uint64_t seed, int bh, int S, int row, int lm,
   const uint64_t base = ((uint64_t)bh * S + row) * 16 + lm;
   return rng_hash(seed, base * 2 + half);
 }
+// S > 128 (attention_long.hip): one hash per (row, lm, 64-key block c64),
+// its four 16-bit slices the block's four key tiles, so key k of row q draws
+// slice (k / 16) & 3 of att_drop_hash_c64(.., q, k % 16, k / 64). NC is 2
+// up to S = 128, where this is att_drop_hash_half's expression. The long
+// kernels draw through this helper and att_drop_keep and nothing else.
+DEV uint64_t att_drop_hash_c64(uint64_t seed, int bh, int S, int row, int lm,
+                               int c64) {
+  const int nc = (S + 63) / 64;
+  const uint64_t base = ((uint64_t)bh * S + row) * 16 + lm;
+  return rng_hash(seed, base * (nc < 2 ? 2 : nc) + c64);
+}
 DEV void att_drop_hash(uint64_t (&z)[2], uint64_t seed, int bh, int S,
                        int row, int lm) {
   z[0] = att_drop_hash_half(seed, bh, S, row, lm, 0);
@@ -254,6 +276,23 @@ DEV void att_drop_bits_lds(unsigned char* bits, uint64_t seed, int bh, int S,
 #pragma unroll
     for (int w = 0; w < 4; ++w)
       v |= (unsigned)att_drop_keep(z, (kb & 1) * 4 + w, keep16) << w;
+    bits[(q >> 2) * 64 + lm * 4 + (q & 3)] = (unsigned char)v;
+  }
+}
+
+// The long form: key block kb's keep bits for the nrows query rows from q0
+// on, same byte layout with q counted from q0; att_drop_hash_c64(.., kb)
+// is the one hash whose slices are the block's four waves.
+DEV void att_drop_bits_lds_long(unsigned char* bits, uint64_t seed, int bh,
+                                int S, int kb, int q0, int nrows,
+                                unsigned keep16, int tid) {
+  for (int u = tid; u < nrows * 16; u += 256) {
+    const int q = u >> 4, lm = u & 15;
+    const uint64_t z[2] = {att_drop_hash_c64(seed, bh, S, q0 + q, lm, kb), 0};
+    unsigned v = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+      v |= (unsigned)att_drop_keep(z, w, keep16) << w;
     bits[(q >> 2) * 64 + lm * 4 + (q & 3)] = (unsigned char)v;
   }
 }

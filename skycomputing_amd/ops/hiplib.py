@@ -112,6 +112,16 @@ def _register_signatures(lib):
         "sky_attn_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
         # sky_attn_bwd_dbias's arguments + job (host FinishJob*): the dbias
         # slab reduction is left pending there
+        # 128 < S <= 4096 (ops/hip/attention_long.hip): flash kernels, keys
+        # on the MFMA rows; no S x S scratch, dot is fp32 [B*h*S]
+        "sky_attn_long_fwd": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, f32, f32, u64, u64],
+        #                     strm qkv  mask out  m    l    B    S    h    d  scale keep salt state
+        "sky_attn_long_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        # strm qkv dout out mask m l dot dqkv | B S h d scale keep salt state
+        "sky_attn_long_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        # sky_attn_long_bwd's arguments + scratch, dbias, dbias dt (as sky_attn_bwd_dbias)
+        "sky_attn_long_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        # sky_attn_long_bwd_dbias's arguments + job (host FinishJob*)
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending

@@ -26,7 +26,7 @@ for S in (256, 512, 1024, 2048, 4096):
     os.environ["SKY_NO_SDPA"] = "1"
     t_dec = bench(lambda: ops.attention(qkv, None, 0.0, False))
     del os.environ["SKY_NO_SDPA"]
-    print(f"S={S:5d} B={B:2d}: default(sdpa) {t_sdpa_d:7.1f}  skyflash {t_flash:7.1f}  decomposed {t_dec:7.1f}")
+    print(f"S={S:5d} B={B:2d}: default {t_sdpa_d:7.1f}  skyflash {t_flash:7.1f}  decomposed {t_dec:7.1f}")
 
 print("fwd+bwd (us):")
 for S in (512, 2048):
@@ -40,4 +40,27 @@ for S in (512, 2048):
     os.environ["SKY_NO_SDPA"] = "1"
     t_dec = bench_bwd(step)
     del os.environ["SKY_NO_SDPA"]
-    print(f"S={S:5d} B={B:2d}: default(sdpa) {t_def:8.1f}  decomposed {t_dec:8.1f}")
+    print(f"S={S:5d} B={B:2d}: default {t_def:8.1f}  decomposed {t_dec:8.1f}")
+
+# The long keys-on-rows kernels (SKY_ATTN_LONG=1) against today's dispatch
+# (SKY_ATTN_LONG=0: sdpa), same process: key mask, dropout 0.1, 4096 tokens.
+print("SKY_ATTN_LONG=1 against =0, mask + dropout 0.1 (us):")
+for S in (256, 512, 1024, 2048):
+    B = 4096 // S
+    qkv = torch.randn(B, S, 3, 16, 64, dtype=torch.bfloat16, device="cuda", requires_grad=True)
+    mask = torch.zeros(B, 1, 1, S, dtype=torch.bfloat16, device="cuda")
+    mask[..., S - S // 5:] = -10000.0
+    def fwd():
+        with torch.no_grad():
+            ops.attention(qkv, mask, 0.1, True)
+    def step():
+        out = ops.attention(qkv, mask, 0.1, True)
+        out.backward(torch.ones_like(out))
+        qkv.grad = None
+    t = {}
+    for flag in ("0", "1"):
+        os.environ["SKY_ATTN_LONG"] = flag
+        t[flag] = (bench(fwd), bench_bwd(step, iters=30))
+    del os.environ["SKY_ATTN_LONG"]
+    print(f"S={S:5d} B={B:2d}: fwd sdpa {t['0'][0]:7.1f} long {t['1'][0]:7.1f}   "
+          f"fwd+bwd sdpa {t['0'][1]:8.1f} long {t['1'][1]:8.1f}")

@@ -26,6 +26,7 @@ __all__ = [
     "attention_context", "attention_block", "ffn_block", "linear_act",
     "linear_residual_layer_norm",
     "embedding_fused", "softmax_cross_entropy", "sgd_step", "adamw_step",
+    "lamb_step",
     "gelu", "swish", "ACT_FNS", "hip_available",
 ]
 
@@ -402,3 +403,13 @@ def adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9,
     return eager.adamw_step(params, grads, exp_avgs, exp_avg_sqs, step, lr,
                             beta1, beta2, eps, weight_decay, master_params,
                             max_grad_norm, no_decay)
+
+
+def lamb_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9,
+              beta2=0.999, eps=1e-6, weight_decay=0.01, master_params=None,
+              max_grad_norm=None, no_decay=None, adapt=None):
+    """Multi-tensor LAMB step (per-tensor trust ratios, the clip folded
+    in); fused HIP path lives in optim.FusedLAMB."""
+    return eager.lamb_step(params, grads, exp_avgs, exp_avg_sqs, step, lr,
+                           beta1, beta2, eps, weight_decay, master_params,
+                           max_grad_norm, no_decay, adapt)

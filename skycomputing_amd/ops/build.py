@@ -30,6 +30,11 @@ CFLAGS = [
 # extra compile flags for check builds, e.g. SKY_HIPCC_FLAGS=-DSKY_GELU_IEEE_MATH
 # (ops/hip/common.h); part of the stamp, so changing them rebuilds
 CFLAGS += shlex.split(os.environ.get("SKY_HIPCC_FLAGS", ""))
+# per-source additions. lamb.hip: no packed fp32 instructions (v_pk_*_f32),
+# so both of its stages round u through the same scalar VALU ops
+FILE_CFLAGS = {
+    "lamb.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _source_hash(sources: list[str]) -> str:
@@ -38,6 +43,7 @@ def _source_hash(sources: list[str]) -> str:
         with open(s, "rb") as f:
             h.update(f.read())
     h.update(" ".join(CFLAGS).encode())
+    h.update(json.dumps(FILE_CFLAGS, sort_keys=True).encode())
     return h.hexdigest()
 
 
@@ -58,7 +64,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objs = []
     for src in sources:
         obj = src.replace(".hip", ".o")
-        cmd = [HIPCC, *CFLAGS, "-x", "hip", "-c", src, "-o", obj]
+        extra = FILE_CFLAGS.get(os.path.basename(src), [])
+        cmd = [HIPCC, *CFLAGS, *extra, "-x", "hip", "-c", src, "-o", obj]
         if verbose:
             print("[skyhip]", " ".join(cmd))
         subprocess.run(cmd, check=True)

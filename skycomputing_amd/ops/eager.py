@@ -247,3 +247,70 @@ def adamw_step(
         if master_params is not None:
             p.copy_(target.to(p.dtype))
     return norm, clip
+
+
+@torch.no_grad()
+def lamb_step(
+    params: list[torch.Tensor],
+    grads: list[torch.Tensor],
+    exp_avgs: list[torch.Tensor],
+    exp_avg_sqs: list[torch.Tensor],
+    step: int,
+    lr: float,
+    beta1: float = 0.9,
+    beta2: float = 0.999,
+    eps: float = 1e-6,
+    weight_decay: float = 0.01,
+    master_params: list[torch.Tensor] | None = None,
+    max_grad_norm: float | None = None,
+    no_decay: list[bool] | None = None,
+    adapt: list[bool] | None = None,
+):
+    """Multi-tensor LAMB in fp32 torch ops; ``step`` is this step's number,
+    counted from 1.
+
+    u = (m/(1-beta1^t)) / (sqrt(v)/sqrt(1-beta2^t) + eps) + wd*p with Adam's
+    moments m and v of the clipped gradient (the clip as in adamw_step), and
+    p -= lr * r * u, where r = ||p|| / ||u|| over the tensor if it adapts
+    and both norms are positive, else 1. Tensors flagged in ``no_decay`` get
+    wd = 0; ``adapt`` (one bool per tensor, all True when None) says which
+    tensors take the ratio. p is the fp32 master where there is one, and
+    the norms are taken over it. Returns ``(norm, clip, norms)``: the first
+    two as adamw_step, ``norms`` an fp32 [3, len(params)] tensor {trust
+    ratio, ||p||, ||u||} (1, 0, 0 for a tensor without a gradient). The
+    ratios stay on the device: nothing here synchronises."""
+    live = [i for i, g in enumerate(grads) if g is not None]
+    norm = clip = None
+    if max_grad_norm is not None and live:
+        sq = torch.stack([grads[i].float().square().sum() for i in live]).sum()
+        norm = sq.sqrt()
+        clip = (max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
+    bc1 = 1.0 - beta1 ** step
+    rsqrt_bc2 = 1.0 / math.sqrt(1.0 - beta2 ** step)
+    device = params[0].device if params else torch.device("cpu")
+    norms = torch.zeros(3, len(params), dtype=torch.float32, device=device)
+    norms[0].fill_(1.0)
+    for i in live:
+        p = params[i]
+        target = master_params[i] if master_params is not None else p
+        m, v = exp_avgs[i], exp_avg_sqs[i]
+        g = grads[i].float()
+        if clip is not None:
+            g = g * clip
+        wd = 0.0 if (no_decay is not None and no_decay[i]) else weight_decay
+        t32 = target.float()
+        m.mul_(beta1).add_(g, alpha=1.0 - beta1)
+        v.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
+        u = (m / bc1).div_(v.sqrt().mul_(rsqrt_bc2).add_(eps))
+        if wd != 0.0:
+            u.add_(t32, alpha=wd)
+        pn = torch.linalg.vector_norm(t32)
+        un = torch.linalg.vector_norm(u)
+        norms[1, i], norms[2, i] = pn, un
+        if adapt is None or adapt[i]:
+            norms[0, i] = torch.where((pn > 0) & (un > 0), pn / un, norms[0, i])
+        t32 = t32 - (lr * norms[0, i]) * u
+        target.copy_(t32.to(target.dtype))
+        if master_params is not None:
+            p.copy_(target.to(p.dtype))
+    return norm, clip, norms

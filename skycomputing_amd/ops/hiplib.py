@@ -70,6 +70,13 @@ def _register_signatures(lib):
         "sky_gradnorm_finish": [u64, u64, i64, u64, f32],  # strm partials n hyper max_norm
         "sky_adamw_step": [u64, u64, i64, u64, f64, f64, f32, f32, i32, i32],
         #                  strm descs n   hyper b1   b2   eps  wd   dt   flags
+        # LAMB (ops/hip/lamb.hip): AdamW's tick and norm kernels, then these
+        "sky_lamb_stage1": [u64, u64, i64, u64, u64, f64, f64, f32, f32, i32, i32],
+        #                   strm descs n   hyper partials b1 b2 eps  wd   dt   flags
+        "sky_lamb_ratios": [u64, u64, u64, u64, u64, i64],
+        #                   strm partials first adapt out n_tensors
+        "sky_lamb_stage2": [u64, u64, i64, u64, u64, f32, f32, i32, i32],
+        #                   strm descs n   hyper ratios eps wd  dt   flags
         "sky_xent_fwd": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, i32],
         #                strm logits labels rowmax logsum rowloss N V ld ignore dt
         "sky_xent_finish": [u64, u64, u64, u64, i64, i64, i64],

@@ -1,10 +1,12 @@
-"""Multi-tensor optimizer launch planning (SGD and AdamW).
+"""Multi-tensor optimizer launch planning (SGD, AdamW and LAMB).
 
 Packs per-parameter {param, grad, master, state...} pointers into a device
 descriptor array (one entry per <=1M-element slab) so the whole stage
 updates in ONE kernel launch (ops/hip/sgd.hip, ops/hip/adamw.hip). SGD rows
 are {p, g, master, momentum, n, 0}; AdamW rows are {p, g, master, m, v, n,
-flags} with flags bit 0 = "no weight decay". The plan is rebuilt only
+flags} with flags bit 0 = "no weight decay"; LAMB rows are AdamW rows with
+the tensor's index in flags bits 32 and up (ops/hip/lamb.hip), next to a
+per-tensor table of first-slab indices. The plan is rebuilt only
 when one of those pointers changes (autograd reuses .grad buffers and the
 optimizer owns the rest, so in steady state this is built once).
 """
@@ -20,7 +22,7 @@ from .hiplib import check
 
 _SLAB = int(os.environ.get("SKY_SGD_SLAB", 1 << 18))  # elements per descriptor (256k default: 1M-elem slabs win standalone (5.5 vs 4.7 TB/s) but LOSE in-app (+0.6 ms/step) - tools/sgd_bench.py + c7 profile)
 
-_PLAN_CACHE: dict = {}  # id(params) -> SGD plan, ("adamw", id(params)) -> AdamW plan
+_PLAN_CACHE: dict = {}  # id(params) -> SGD plan, ("adamw" | "lamb", id(params)) -> that plan
 
 
 def _build_plan(params, grads, masters, *states, flags=None):
@@ -46,13 +48,17 @@ def _build_plan(params, grads, masters, *states, flags=None):
                 cnt, flag,
             ])
             off += cnt
+    return _upload(rows, torch.int64, params[0].device), len(rows)
+
+
+def _upload(values, dtype, device):
     # pinned staging so the H2D copy is legal inside hipGraph capture
-    cpu = torch.tensor(rows, dtype=torch.int64)
+    cpu = torch.tensor(values, dtype=dtype)
     try:
         cpu = cpu.pin_memory()
     except RuntimeError:
         pass
-    return cpu.to(params[0].device, non_blocking=True), len(rows)
+    return cpu.to(device, non_blocking=True)
 
 
 def _plan_signature(params, grads, masters, *states) -> tuple:
@@ -141,3 +147,83 @@ def multi_tensor_adamw(params, grads, masters, exp_avgs, exp_avg_sqs, hyper,
                            beta1, beta2, eps, wd, dt, flags),
         "sky_adamw_step",
     )
+
+
+_LAMB_TENSOR_SHIFT = 32  # flags bits 32..62: the row's tensor index
+
+
+def _build_lamb_plan(params, grads, masters, exp_avgs, exp_avg_sqs, no_decay,
+                     adapt):
+    """(desc, n_slabs, n_tensors, first, adapt, partials, norms).
+
+    desc: AdamW rows with the tensor index above bit 32. first: int32
+    [n_tensors + 1], tensor k owns slabs first[k] .. first[k+1]-1 (the
+    splitter walks the tensors in order). adapt: int32 [n_tensors].
+    partials: fp32 [2 * n_slabs], per slab {sum p^2, sum u^2}; its head
+    doubles as the gradient norm's n_slabs partials, which are consumed
+    before stage 1 writes. norms: fp32 [3, n_tensors], the planes {trust
+    ratio, ||p||, ||u||}; the ratios start at 1."""
+    assert _SLAB % 8 == 0, _SLAB
+    for group in (params, grads, masters, exp_avgs, exp_avg_sqs):
+        for t in group or ():
+            assert t.data_ptr() % 16 == 0, (
+                f"tensor of shape {tuple(t.shape)} is not 16-byte aligned")
+    device = params[0].device
+    flags = [(1 if nd else 0) | (k << _LAMB_TENSOR_SHIFT)
+             for k, nd in enumerate(no_decay)]
+    desc, n = _build_plan(params, grads, masters, exp_avgs, exp_avg_sqs,
+                          flags=flags)
+    first = [0]
+    for p in params:
+        first.append(first[-1] + -(-p.numel() // _SLAB))
+    assert first[-1] == n and n < 2 ** 31, (first[-1], n)
+    n_tensors = len(params)
+    norms = torch.zeros(3, n_tensors, dtype=torch.float32, device=device)
+    norms[0].fill_(1.0)
+    return (desc, n, n_tensors, _upload(first, torch.int32, device),
+            _upload([1 if a else 0 for a in adapt], torch.int32, device),
+            torch.zeros(2 * n, dtype=torch.float32, device=device), norms)
+
+
+def multi_tensor_lamb(params, grads, masters, exp_avgs, exp_avg_sqs, hyper,
+                      beta1, beta2, eps, wd, no_decay, adapt,
+                      max_grad_norm=None):
+    """One LAMB step over all tensors (ops/hip/lamb.hip): the gradient norm
+    and clip factor (when ``max_grad_norm`` is set) and the step counter's
+    tick through AdamW's kernels, then stage 1 (moments, per-slab sums of
+    p^2 and u^2), the per-tensor trust ratios, and stage 2 (the update).
+    ``hyper`` is the optimizer's AdamW hyper block; nothing here changes
+    between the replays of a captured step. ``no_decay``, ``adapt``: one
+    bool per parameter. Returns the plan's fp32 [3, n_tensors] tensor
+    {trust ratio, ||p||, ||u||}, which the kernels refill every step."""
+    sig = _plan_signature(params, grads, masters, exp_avgs, exp_avg_sqs)
+    sig += tuple(bool(nd) for nd in no_decay) + tuple(bool(a) for a in adapt)
+    desc, n, n_tensors, first, adapt_dev, partials, norms = _cached_plan(
+        ("lamb", id(params)), sig,
+        lambda: _build_lamb_plan(params, grads, masters, exp_avgs,
+                                 exp_avg_sqs, no_decay, adapt))
+    lib = hiplib.require()
+    dt = 1 if params[0].dtype == torch.bfloat16 else 0
+    flags = 1 if masters is not None else 0
+    stream = torch.cuda.current_stream().cuda_stream
+    if max_grad_norm is not None:
+        check(lib.sky_gradnorm_partials(stream, desc.data_ptr(), n,
+                                        partials.data_ptr(), dt),
+              "sky_gradnorm_partials")
+        check(lib.sky_gradnorm_finish(stream, partials.data_ptr(), n,
+                                      hyper.data_ptr(), max_grad_norm),
+              "sky_gradnorm_finish")
+    check(lib.sky_adamw_tick(stream, hyper.data_ptr(), beta1, beta2),
+          "sky_adamw_tick")
+    check(lib.sky_lamb_stage1(stream, desc.data_ptr(), n, hyper.data_ptr(),
+                              partials.data_ptr(), beta1, beta2, eps, wd, dt,
+                              flags),
+          "sky_lamb_stage1")
+    check(lib.sky_lamb_ratios(stream, partials.data_ptr(), first.data_ptr(),
+                              adapt_dev.data_ptr(), norms.data_ptr(),
+                              n_tensors),
+          "sky_lamb_ratios")
+    check(lib.sky_lamb_stage2(stream, desc.data_ptr(), n, hyper.data_ptr(),
+                              norms.data_ptr(), eps, wd, dt, flags),
+          "sky_lamb_stage2")
+    return norms

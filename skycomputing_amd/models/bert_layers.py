@@ -23,6 +23,8 @@ Dataflow tuples between pipeline stages:
   BertPooler(hidden, ext_mask)              -> pooled [B, H]
   BertTailForClassification(pooled)         -> logits [B, C]
   BertLMHead(hidden, ext_mask)              -> logits [B, S, Vpad]  (pretraining)
+With config key packed_sequences the ext_mask slot carries int32 segment ids
+[B, S] (several sequences per row, ops.attention's segment_ids).
 """
 
 from __future__ import annotations
@@ -143,7 +145,12 @@ class BertSelfOutput(nn.Module):
 class BertEmbeddings(nn.Module):
     """Word+position+type embeddings, LN, dropout; also builds the additive
     extended attention mask (1-m)*-10000 carried down the pipeline
-    (reference: scaelum/model/bert_layers.py:171-212)."""
+    (reference: scaelum/model/bert_layers.py:171-212).
+
+    Config key packed_sequences (default False): attention_mask holds
+    segment ids, one contiguous run per packed sequence and padding as a run
+    of its own (id 0 at the tail); they go down the pipeline as int32 [B, S]
+    in the ext_mask slot and the position ids restart at every run start."""
 
     def __init__(self, config):
         super().__init__()
@@ -165,9 +172,13 @@ class BertEmbeddings(nn.Module):
             token_type_ids = torch.zeros_like(input_ids)
         if attention_mask is None:
             attention_mask = torch.ones(B, S, device=dev, dtype=torch.long)
-        # additive extended mask, broadcast to [B,1,1,S]
-        ext_mask = (1.0 - attention_mask[:, None, None, :].to(self.word_embeddings.weight.dtype)) * -10000.0
         position_ids = torch.arange(S, device=dev, dtype=torch.long).unsqueeze(0).expand(B, S)
+        if getattr(self.config, "packed_sequences", False):
+            ext_mask = attention_mask.to(torch.int32)
+            position_ids = position_ids - ops.eager.seg_runs(attention_mask)[0]
+        else:
+            # additive extended mask, broadcast to [B,1,1,S]
+            ext_mask = (1.0 - attention_mask[:, None, None, :].to(self.word_embeddings.weight.dtype)) * -10000.0
         emb = ops.embedding_fused(
             input_ids, token_type_ids, position_ids,
             self.word_embeddings.weight, self.position_embeddings.weight,
@@ -202,11 +213,13 @@ class BertLayerHead(nn.Module):
         # (what self.output(self.attention(hidden, ext_mask), hidden)
         # computes): on GPU a single autograd node, see ops.attention_block
         att, out = self.attention, self.output
+        # an integer ext_mask is BertEmbeddings' packed-sequence segment ids
+        packed = ext_mask is not None and not ext_mask.is_floating_point()
         y = ops.attention_block(
-            hidden, ext_mask, att.qkv.weight, att.qkv.bias, att.num_heads,
-            att.dropout_p, out.dense.weight, out.dense.bias,
+            hidden, None if packed else ext_mask, att.qkv.weight,
+            att.qkv.bias, att.num_heads, att.dropout_p, out.dense.weight, out.dense.bias,
             out.layer_norm.weight, out.layer_norm.bias, out.layer_norm.eps,
-            out.dropout_p, self.training)
+            out.dropout_p, self.training, ext_mask if packed else None)
         return y, ext_mask
 
     def layer_flops(self, batch: int, seq: int) -> float:

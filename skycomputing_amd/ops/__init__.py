@@ -113,9 +113,21 @@ def attention_context(q, k, v, mask, dropout_p: float = 0.0, training: bool = Fa
     return eager.attention_context(q, k, v, mask, dropout_p, training)
 
 
-def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
+def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
+              segment_ids=None):
     """Multi-head attention over a packed qkv tensor [B, S, 3, h, d];
     returns [B, S, h*d].
+
+    segment_ids (packed sequences): integer [B, S] in the place of mask;
+    query q attends key k iff segment_ids[b, q] == segment_ids[b, k]. Equal
+    ids must form one contiguous run per row and distinct runs carry
+    distinct ids; padding is an ordinary run (conventionally id 0 at the
+    tail) whose tokens attend each other. GPU, bf16, d=64, 128 < S <= 4096:
+    the segment form of the chunked kernels at every such S unless
+    SKY_ATTN_LONG=0 (only the chunks a block's runs touch are visited; the
+    run rule is not checked there, a check would synchronise); other GPU
+    shapes: torch sdpa with the dense boolean mask; CPU: the eager path,
+    which raises ValueError for ids that break the run rule.
 
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
     (FusedAttentionFn); 128 < S <= 4096: its chunked form where
@@ -127,6 +139,32 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False):
 
     B, S, three, h, d = qkv.shape
     scale = 1.0 / math.sqrt(d)
+    if segment_ids is not None:
+        if mask is not None:
+            raise ValueError("attention: give either mask or segment_ids, not both")
+        if segment_ids.shape != (B, S) or segment_ids.is_floating_point():
+            raise ValueError("segment_ids must be an integer tensor [B, S]")
+        if (
+            qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64
+            and 128 < S <= 4096 and _use_hip(qkv)
+            and os.environ.get("SKY_ATTN_LONG") != "0"
+        ):
+            from .functions import FusedAttentionFn
+
+            out = FusedAttentionFn.apply(qkv, None, scale, dropout_p, training,
+                                         segment_ids)
+            return out.reshape(B, S, h * d)
+        q, k, v = _split_heads(qkv)
+        same = eager.segment_mask(segment_ids, check=not qkv.is_cuda)
+        if qkv.is_cuda:
+            ctx = torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, attn_mask=same,
+                dropout_p=dropout_p if training else 0.0)
+        else:
+            dense = torch.zeros(same.shape, dtype=qkv.dtype).masked_fill_(
+                ~same, float("-inf"))
+            ctx = eager.attention_context(q, k, v, dense, dropout_p, training)
+        return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
     if (
         qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64
         and hiplib.available() and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
@@ -211,7 +249,7 @@ def linear_residual_layer_norm(x, weight, bias, ln_weight, ln_bias,
 def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
                     attn_dropout_p: float, out_weight, out_bias, ln_weight,
                     ln_bias, eps: float = 1e-12, hidden_dropout_p: float = 0.0,
-                    training: bool = False):
+                    training: bool = False, segment_ids=None):
     """The attention third of an encoder block:
     LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
     for hidden [B, S, H], mask [B, 1, 1, S] additive or None.
@@ -223,12 +261,13 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     attention backward kernels and sums hidden's two gradients inside the
     qkv dgrad GEMM. Everything else — CPU, fp32, long sequences,
     SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
-    paths — is the composition of ops.linear, ops.attention and
+    paths, and segment_ids (packed sequences, see ops.attention) — is the
+    composition of ops.linear, ops.attention and
     ops.linear_residual_layer_norm."""
     B, S, H = hidden.shape
     d = H // num_heads
     if (
-        hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
+        segment_ids is None and hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
         and qkv_bias is not None and out_bias is not None
         and hiplib.available()
         and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
@@ -251,7 +290,7 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
                 out_weight, out_bias, ln_weight, ln_bias, eps, hp
             )
     qkv = linear(hidden, qkv_weight, qkv_bias).view(B, S, 3, num_heads, d)
-    attn = attention(qkv, mask, attn_dropout_p, training)
+    attn = attention(qkv, mask, attn_dropout_p, training, segment_ids)
     return linear_residual_layer_norm(
         attn, out_weight, out_bias, ln_weight, ln_bias, eps, hidden,
         hidden_dropout_p, training)

@@ -90,6 +90,41 @@ def attention_context(
     return torch.matmul(probs, v)
 
 
+def seg_runs(segment_ids: torch.Tensor):
+    """Per token of integer ids [B, S]: the start and the (exclusive) end of
+    its run of equal neighbours, two int64 [B, S]."""
+    B, S = segment_ids.shape
+    pos = torch.arange(S, device=segment_ids.device).expand(B, S)
+    new = torch.ones(B, S, dtype=torch.bool, device=segment_ids.device)
+    new[:, 1:] = segment_ids[:, 1:] != segment_ids[:, :-1]
+    last = new.roll(-1, 1)  # position 0 starts a run, so S - 1 ends one
+    start = torch.where(new, pos, 0).cummax(1).values
+    end = torch.where(last, pos + 1, S).flip(1).cummin(1).values.flip(1)
+    return start, end
+
+
+def seg_bounds(segment_ids: torch.Tensor) -> torch.Tensor:
+    """What sky_attn_seg_bounds computes: int32 [B, ceil(S/64), 2], per
+    64-token block the run start of its first token and the run end of its
+    last one."""
+    start, end = seg_runs(segment_ids)
+    first = torch.arange(0, segment_ids.shape[1], 64, device=segment_ids.device)
+    last = (first + 63).clamp(max=segment_ids.shape[1] - 1)
+    return torch.stack([start[:, first], end[:, last]], -1).to(torch.int32)
+
+
+def segment_mask(segment_ids: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """Boolean [B, 1, S, S], true where query and key carry the same id
+    (packed sequences). check: raise ValueError unless equal ids form one
+    contiguous run per row; it synchronises, so GPU callers leave it out."""
+    same = segment_ids[:, None, :, None] == segment_ids[:, None, None, :]
+    if check:
+        start, end = seg_runs(segment_ids)
+        if not torch.equal(same.sum(-1)[:, 0], end - start):
+            raise ValueError("segment_ids: equal ids must form one contiguous run per row")
+    return same
+
+
 def linear_act(
     x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, act: str = "gelu"
 ) -> torch.Tensor:

@@ -343,10 +343,22 @@ def attn_long_enabled(S: int) -> bool:
             and _ATTN_LONG_DEFAULT[0] < S <= _ATTN_LONG_DEFAULT[1])
 
 
-def _attn_fwd(qkv, mask, scale, keep):
+def attn_seg_bounds(ids):
+    """sky_attn_seg_bounds on int32 segment ids [B, S], 128 < S <= 4096: per
+    64-token block the run start of its first token and the run end of its
+    last one, int32 [B, ceil(S/64), 2] (eager.seg_bounds)."""
+    B, S = ids.shape
+    bounds = torch.empty(B, (S + 63) // 64, 2, dtype=torch.int32, device=ids.device)
+    check(hiplib.require().sky_attn_seg_bounds(_stream(), ptr(ids), ptr(bounds), B, S),
+          "sky_attn_seg_bounds")
+    return bounds
+
+
+def _attn_fwd(qkv, mask, scale, keep, seg=None):
     """sky_attn_fwd (S <= 128) or sky_attn_long_fwd on a contiguous packed
     qkv [B, S, 3, h, 64]; draws the dropout salt when keep < 1. Returns
-    (out [B, S, h, d], m, lsum, salt)."""
+    (out [B, S, h, d], m, lsum, salt). seg = (ids, bounds): the segment
+    form sky_attn_long_seg_fwd, S > 128 only."""
     lib = hiplib.require()
     B, S, _, h, d = qkv.shape
     out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
@@ -354,10 +366,14 @@ def _attn_fwd(qkv, mask, scale, keep):
     lsum = torch.empty_like(m)
     salt = _next_seed() if keep < 1.0 else 0
     state = rng_state()
-    name = "sky_attn_long_fwd" if S > ATTN_SMAX else "sky_attn_fwd"
+    if seg is not None:
+        name, masks = "sky_attn_long_seg_fwd", (ptr(seg[0]), ptr(seg[1]))
+    else:
+        name = "sky_attn_long_fwd" if S > ATTN_SMAX else "sky_attn_fwd"
+        masks = (ptr(mask),)
     check(
         getattr(lib, name)(
-            _stream(), ptr(qkv), ptr(mask), ptr(out), ptr(m), ptr(lsum),
+            _stream(), ptr(qkv), *masks, ptr(out), ptr(m), ptr(lsum),
             B, S, h, d, scale, keep, salt, state.data_ptr(),
         ),
         name,
@@ -406,20 +422,29 @@ class FusedAttentionFn(torch.autograd.Function):
     recompute + hipBLASLt batched GEMMs + HIP softmax-backward).
 
     qkv: [B, S, 3, h, d] (d = 64), mask: [B, 1, 1, S] additive or None.
+    segment_ids (packed sequences, 128 < S <= 4096, no mask): integer
+    [B, S], q attends k iff their ids are equal; equal ids must form one
+    contiguous run per row, which is NOT checked here (a check would
+    synchronise). The block bounds are computed once and saved for backward.
     Returns [B, S, h, d].
     """
 
     @staticmethod
-    def forward(ctx, qkv, mask, scale, dropout_p, training):
+    def forward(ctx, qkv, mask, scale, dropout_p, training, segment_ids=None):
         B, S, three, h, d = qkv.shape
         assert three == 3 and d == 64 and S <= ATTN_LONG_SMAX
         qkv = qkv.contiguous()
         mask = mask.contiguous() if mask is not None else None
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
-        out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep)
+        seg = ()
+        if segment_ids is not None:
+            assert mask is None and S > ATTN_SMAX and segment_ids.shape == (B, S)
+            ids = segment_ids.to(torch.int32).contiguous()
+            seg = (ids, attn_seg_bounds(ids))
+        out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep, seg or None)
         # the long backward takes its row dots from dO * O
         extra = (out,) if S > ATTN_SMAX else ()
-        ctx.save_for_backward(qkv, mask, m, lsum, *extra)
+        ctx.save_for_backward(qkv, mask, m, lsum, *extra, *seg)
         ctx.scale, ctx.keep, ctx.salt = scale, keep, salt
         return out
 
@@ -435,13 +460,15 @@ class FusedAttentionFn(torch.autograd.Function):
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)
             dot = torch.empty(B * h * S, dtype=torch.float32, device=dev)
-            check(
-                lib.sky_attn_long_bwd(*_attn_long_bwd_args(
-                    qkv, dout, extra[0], mask, m, lsum, dot, dqkv, ctx.scale,
-                    ctx.keep, ctx.salt)),
-                "sky_attn_long_bwd",
-            )
-            return dqkv, None, None, None, None
+            args = _attn_long_bwd_args(
+                qkv, dout, extra[0], mask, m, lsum, dot, dqkv, ctx.scale,
+                ctx.keep, ctx.salt)
+            if len(extra) == 3:  # (out, ids, bounds): the segment form
+                args = args[:4] + (ptr(extra[1]), ptr(extra[2])) + args[5:]
+                check(lib.sky_attn_long_seg_bwd(*args), "sky_attn_long_seg_bwd")
+            else:
+                check(lib.sky_attn_long_bwd(*args), "sky_attn_long_bwd")
+            return dqkv, None, None, None, None, None
         if os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1":
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)

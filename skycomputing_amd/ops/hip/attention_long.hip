@@ -17,10 +17,19 @@
 // No S x S tensor and no scratch beyond dot [B*h*S] fp32 exists anywhere.
 // Dropout: att_drop_hash_c64 + att_drop_keep (attn_common.h), regenerated
 // in both backward kernels from (salt, state).
+// Segment mode (SEG, packed sequences): query q sees key k iff their segment
+// ids are equal, and equal ids form one contiguous run per row. A 64-token
+// block then walks only the chunks between the run start of its first token
+// and the run end of its last one (attn_seg_bounds_kernel's table; the
+// relation is symmetric, so the table serves query and key blocks alike).
+// The dropout hashes take absolute (row, key) indices: skipping a chunk
+// moves no mask bit.
 
 #include "attn_common.h"
 
 #define ATL_SMAX 4096
+
+typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 // Every kernel of this file is compiled without the packed fp32 VALU ops
 // (v_pk_mul_f32, v_pk_fma_f32, v_pk_add_f32). With them the compiler packs
@@ -76,6 +85,39 @@ DEV void atl_drop_hash_chunk(uint64_t (&z)[4][2], uint64_t seed, int bh, int S,
   }
 }
 
+// SEG: the segment ids of the 128-key chunk at k0 in the LDS slot of the
+// fp32 key mask, as int32; keys >= S repeat key S-1 (atl_seg_mask4 nulls
+// them by position)
+DEV void atl_seg_ids_lds_at(int* sk, const int* __restrict__ ids, int b, int S,
+                            int k0, int tid) {
+  if (tid < ATT_SMAX) {
+    const int key = k0 + tid;
+    sk[tid] = ids[(size_t)b * S + (key < S ? key : S - 1)];
+  }
+}
+// the additive mask of tile mt's four keys lg*4.. against the lane's own id:
+// 0 for the same segment, -3e38 (the out-of-range key value) for another
+// segment and for chunk positions >= nk
+DEV f32x4 atl_seg_mask4(const int* sk, int mt, int lg, int own, int nk) {
+  const i32x4 id = *(const i32x4*)(sk + mt * 16 + lg * 4);
+  f32x4 mv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    mv[r] = (id[r] == own && mt * 16 + lg * 4 + r < nk) ? 0.f : -3.0e38f;
+  return mv;
+}
+// SEG: the chunk range [c0, c1) of 64-token block blk of batch row b, from
+// the bounds table [B][QB][lo, hi); clamped to the row, so that no table
+// content can send a walk out of bounds
+DEV void atl_seg_chunks(int& c0, int& c1, const int* __restrict__ bounds,
+                        int b, int QB, int blk, int NCH) {
+  const int* bd = bounds + ((size_t)b * QB + blk) * 2;
+  const int lo = bd[0], hi = bd[1];
+  c0 = lo > 0 ? lo / 128 : 0;
+  c1 = (hi + 127) / 128;
+  c1 = c1 < NCH ? c1 : NCH;
+}
+
 // ---------------------------------------------------------------------------
 // Forward. One block per (b, h, 64-query block), a wave owns 16 queries
 // (fragments from global). LDS: K chunk @0, V chunk @16K, the chunk's key
@@ -86,12 +128,14 @@ DEV void atl_drop_hash_chunk(uint64_t (&z)[4][2], uint64_t seed, int bh, int S,
 #define ATL_MASK_OFF KR_AUX_OFF
 #define ATL_FWD_LDS (KR_AUX_OFF + 512)
 
-template <bool HAS_MASK>
+// SEG: mask points at the int32 segment ids [B][S], bounds at the table.
+template <bool HAS_MASK, bool SEG = false>
 ATL_KERNEL void attn_fwd_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
     ushort_t* __restrict__ out, float* __restrict__ m_io,
     float* __restrict__ l_io, int B, int S, int h, float scale, float keep,
-    uint64_t salt, const unsigned long long* __restrict__ state) {
+    uint64_t salt, const unsigned long long* __restrict__ state,
+    const int* __restrict__ bounds) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int l = tid & 63;
@@ -122,28 +166,44 @@ ATL_KERNEL void attn_fwd_long_kernel(
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
     bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+  const int* ids = (const int*)mask;
+  int kc0 = 0, kc1 = NCH, qid = 0;
+  if constexpr (SEG) {
+    atl_seg_chunks(kc0, kc1, bounds, b, QB, qb, NCH);
+    qid = ids[(size_t)b * S + qc];
+  }
 
   // Chunk 0 always holds key 0 and additive masks are finite (-10000), so m
   // is a real score after chunk 0. Before it, m = -3e38 gives alpha =
   // exp(-3e38 - m_new) = 0 against l = 0 and O = 0; later, a jump of m by
   // 1e4 (a chunk of masked keys followed by a visible one) gives alpha = 0
   // as well, which is the correct weight of the terms so far.
+  // SEG: the walk may start past chunk 0, and a lane can meet chunks with no
+  // key of its segment before its run begins (the block's range starts at
+  // the run of its FIRST token). There every score is exactly -3e38, m_new
+  // stays at the finite -3e38 (alpha = exp(0) = 1 against l = 0 and O = 0),
+  // and the exponent base is held at >= -1e30, so p = exp(-3e38 + 1e30) is
+  // an exact 0 where exp(-3e38 - m_new) would be 1: l and oacc reach the
+  // lane's first visible chunk as exact zeros, and no inf - inf can form
+  // because m is never infinite. With a visible key m_new is a real score
+  // and the clamp does nothing.
   float m = -3.0e38f, lsum = 0.f;
   f32x4 oacc[4];
   att_zero(oacc);
 
 #pragma clang loop unroll(disable)
-  for (int kc = 0; kc < NCH; ++kc) {
+  for (int kc = kc0; kc < kc1; ++kc) {
     const int k0 = kc * 128;
     const int nk = S - k0 < 128 ? S - k0 : 128;
     const int NT = (nk + 15) / 16;
     const int NP = (nk + 31) / 32;  // key-tile pairs = PV contraction steps
-    if (kc) __syncthreads();        // every wave is done with the last chunk
+    if (kc != kc0) __syncthreads();  // every wave is done with the last chunk
     // whole tile pairs are staged; tokens >= S re-read token S-1, finite
     // values that the -3e38 mask (scores) and the zero P (PV) null
     att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
     att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
-    att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    if constexpr (SEG) atl_seg_ids_lds_at((int*)mk, ids, b, S, k0, tid);
+    else att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (!active) continue;
@@ -157,7 +217,9 @@ ATL_KERNEL void attn_fwd_long_kernel(
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
       if (mt >= NT) continue;
-      const f32x4 mv = att_mask_keys4(mk, mt, lgc);
+      f32x4 mv;
+      if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
+      else mv = att_mask_keys4(mk, mt, lgc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float zz = sacc[mt][r] * scale + mv[r];
@@ -170,6 +232,7 @@ ATL_KERNEL void attn_fwd_long_kernel(
     const float m_new = fmaxf(m, mx);
     const float alpha = __expf(m - m_new);
     m = m_new;
+    const float m_exp = SEG ? fmaxf(m_new, -1.0e30f) : m_new;
     uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     if (keep < 1.f) atl_drop_hash_chunk(z, seed, bh, S, q, lg, kc);
     // unnormalised p (the sum takes it before dropout), dropped in place;
@@ -180,7 +243,7 @@ ATL_KERNEL void attn_fwd_long_kernel(
       if (mt >= NT) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float p = __expf(sacc[mt][r] - m_new);
+        float p = __expf(sacc[mt][r] - m_exp);
         sm += p;
         if (keep < 1.f) p = att_drop_keep(z[r], mt, keep16) ? p * inv_keep : 0.f;
         sacc[mt][r] = p;
@@ -226,14 +289,15 @@ ATL_KERNEL void attn_fwd_long_kernel(
 #define ATL_SUM_OFF (KR_AUX_OFF + 512)
 #define ATL_DQ_LDS (KR_AUX_OFF + 512 + 1024)
 
-template <bool HAS_MASK, bool DBIAS>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false>
 ATL_KERNEL void attn_bwd_dq_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ out, const ushort_t* __restrict__ mask,
     const float* __restrict__ m_io, const float* __restrict__ l_io,
     float* __restrict__ dot_out, ushort_t* __restrict__ dqkv, int B, int S,
     int h, float scale, float keep, uint64_t salt,
-    const unsigned long long* __restrict__ state, float* __restrict__ dbscr) {
+    const unsigned long long* __restrict__ state, float* __restrict__ dbscr,
+    const int* __restrict__ bounds) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int l = tid & 63;
@@ -285,19 +349,28 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
   if (active && lg == 0 && q < S) dot_out[(size_t)bh * S + q] = dot;
   const float mrow = m_io[(size_t)bh * S + qc];
   const float lrow = 1.f / l_io[(size_t)bh * S + qc];
+  // SEG: a key of another segment gets the additive -3e38, so P, rebuilt
+  // from the saved m and 1/l, is exp(-huge) = 0 and dS with it
+  const int* ids = (const int*)mask;
+  int kc0 = 0, kc1 = NCH, qid = 0;
+  if constexpr (SEG) {
+    atl_seg_chunks(kc0, kc1, bounds, b, QB, qb, NCH);
+    qid = ids[(size_t)b * S + qc];
+  }
 
   f32x4 qacc[4];
   att_zero(qacc);
 #pragma clang loop unroll(disable)
-  for (int kc = 0; kc < NCH; ++kc) {
+  for (int kc = kc0; kc < kc1; ++kc) {
     const int k0 = kc * 128;
     const int nk = S - k0 < 128 ? S - k0 : 128;
     const int NT = (nk + 15) / 16;
     const int NP = (nk + 31) / 32;
-    if (kc) __syncthreads();
+    if (kc != kc0) __syncthreads();
     att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
     att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
-    att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    if constexpr (SEG) atl_seg_ids_lds_at((int*)mk, ids, b, S, k0, tid);
+    else att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (!active) continue;
@@ -316,7 +389,9 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
       for (int t = 0; t < 2; ++t) {
         const int mt = 2 * kp + t;
         if (mt >= NT) continue;  // s2[t] stays zero: a null dS tile
-        const f32x4 mv = att_mask_keys4(mk, mt, lgc);
+        f32x4 mv;
+        if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
+        else mv = att_mask_keys4(mk, mt, lgc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + mt * 16 + lg * 4 + r;
@@ -369,15 +444,18 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
 #define ATL_BITS_OFF (KR_AUX_OFF + 1536)
 #define ATL_SUM2_OFF (KR_AUX_OFF + 1536 + 2048)
 #define ATL_DKV_LDS (KR_AUX_OFF + 1536 + 2048 + 2048)
+// SEG: the chunk's query ids, int32 [128], one more word array @37.5K
+#define ATL_QID_OFF ATL_DKV_LDS
+#define ATL_DKV_SEG_LDS (ATL_DKV_LDS + 512)
 
-template <bool HAS_MASK, bool DBIAS>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false>
 ATL_KERNEL void attn_bwd_dkv_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
     const float* __restrict__ l_io, const float* __restrict__ dot_in,
     ushort_t* __restrict__ dqkv, int B, int S, int h, float scale, float keep,
     uint64_t salt, const unsigned long long* __restrict__ state,
-    float* __restrict__ dbscr) {
+    float* __restrict__ dbscr, const int* __restrict__ bounds) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int l = tid & 63;
@@ -417,17 +495,26 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
   float mv = 0.f;
   if (HAS_MASK && key < S) mv = bf16_to_f32(mask[(size_t)b * S + key]);
   if (key >= S) mv = -3.0e38f;
+  // SEG: the query chunks of key block kb's range; the lane's key id from
+  // global, as the key mask above
+  const int* ids = (const int*)mask;
+  int* sq = (int*)lds_at(lds, ATL_QID_OFF);
+  int qc0 = 0, qc1 = NCH, kid = 0;
+  if constexpr (SEG) {
+    atl_seg_chunks(qc0, qc1, bounds, b, QB, kb, NCH);
+    kid = ids[(size_t)b * S + kc];
+  }
 
   f32x4 kacc[4], vacc[4];
   att_zero(kacc);
   att_zero(vacc);
 #pragma clang loop unroll(disable)
-  for (int qch = 0; qch < NCH; ++qch) {
+  for (int qch = qc0; qch < qc1; ++qch) {
     const int q0 = qch * 128;
     const int nq = S - q0 < 128 ? S - q0 : 128;
     const int NT = (nq + 15) / 16;
     const int NP = (nq + 31) / 32;
-    if (qch) __syncthreads();  // the one barrier before LDS is reused
+    if (qch != qc0) __syncthreads();  // the one barrier before LDS is reused
     att_glds_rows(qbase, ts, q0, NP * 32, true, S, lds, ATL_Q_OFF, tid);
     att_glds_rows(dobase, dots, q0, NP * 32, true, S, lds, ATL_DO_OFF, tid);
     // rows >= S: 1/l = 0 and a false valid flag null P, dot = 0 keeps dS finite
@@ -437,6 +524,7 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
       st[tid] = live ? m_io[(size_t)bh * S + row] : 0.f;
       st[128 + tid] = live ? 1.f / l_io[(size_t)bh * S + row] : 0.f;
       st[256 + tid] = live ? dot_in[(size_t)bh * S + row] : 0.f;
+      if constexpr (SEG) sq[tid] = ids[(size_t)b * S + (live ? row : S - 1)];
     }
     if (keep < 1.f)
       att_drop_bits_lds_long(bits, seed, bh, S, kb, q0, NP * 32, keep16, tid);
@@ -473,10 +561,13 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
         unsigned kbits = 0xFFFFFFFFu;
         if (keep < 1.f)
           kbits = *(const unsigned*)(bits + ((qt * 4 + lgc) * 16 + lmc) * 4);
+        i32x4 qid4 = {0, 0, 0, 0};
+        if constexpr (SEG) qid4 = *(const i32x4*)(sq + qt * 16 + lgc * 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = q0 + qt * 16 + lg * 4 + r;
-          const float p = att_prob(s4[r], scale, mv, m4[r], il4[r],
+          const float mvr = (SEG && qid4[r] != kid) ? -3.0e38f : mv;
+          const float p = att_prob(s4[r], scale, mvr, m4[r], il4[r],
                                    qq < S && key < S);
           const bool kbit = (kbits >> (8 * r + w)) & 1u;
           float pdv = p, dp = d4[r];
@@ -545,7 +636,7 @@ SKY_EXPORT int sky_attn_long_fwd(uint64_t stream, uint64_t qkv, uint64_t mask,
                 (hipStream_t)stream, (const ushort_t*)qkv,
                 (const ushort_t*)mask, (ushort_t*)out, (float*)m, (float*)lsum,
                 (int)B, (int)S, (int)h, scale, keep, salt,
-                (const unsigned long long*)state);
+                (const unsigned long long*)state, (const int*)nullptr);
   LAUNCH_CHECK();
   return 0;
 }
@@ -564,12 +655,13 @@ static void launch_attn_long_bwd(hipStream_t s, uint64_t qkv, uint64_t dout,
                 (const ushort_t*)out, (const ushort_t*)mask, (const float*)m,
                 (const float*)lsum, (float*)dot, (ushort_t*)dqkv, (int)B,
                 (int)S, (int)h, scale, keep, salt,
-                (const unsigned long long*)state, dbscr);
+                (const unsigned long long*)state, dbscr, (const int*)nullptr);
   ATT_LAUNCH_HM(mask != 0, (attn_bwd_dkv_long_kernel<HM, DBIAS>), grid,
                 ATL_DKV_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
                 (const ushort_t*)mask, (const float*)m, (const float*)lsum,
                 (const float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h,
-                scale, keep, salt, (const unsigned long long*)state, dbscr);
+                scale, keep, salt, (const unsigned long long*)state, dbscr,
+                (const int*)nullptr);
 }
 
 // out: the forward's output [B,S,h,d]; dot: fp32 [B*h*S], written by the
@@ -637,4 +729,107 @@ SKY_EXPORT int sky_attn_long_bwd_dbias_parts(
   return attn_long_bwd_dbias_impl(stream, qkv, dout, out, mask, m, lsum, dot,
                                   dqkv, B, S, h, d, scale, keep, salt, state,
                                   scratch, dbias, dbias_dt, (SkyFinishJob*)job);
+}
+
+// ---------------------------------------------------------------------------
+// Segment bounds. One block per batch row; thread t owns tokens 16t..16t+15
+// (S <= 4096). A neighbour compare marks run starts and run ends; the latest
+// start at or before a token is a prefix-max over positions, the earliest end
+// after it a suffix-min, both scanned over the 256 thread totals in LDS.
+// bounds[b][blk] = {run start of token 64*blk, run end (exclusive) of token
+// min(64*blk + 63, S - 1)}: 0 <= lo <= 64*blk < hi <= S for any ids.
+ATL_NO_PK_F32 __global__ __launch_bounds__(256) void attn_seg_bounds_kernel(
+    const int* __restrict__ ids, int* __restrict__ bounds, int S) {
+  __shared__ int pmax[256], smin[256];
+  const int tid = threadIdx.x;
+  const int* row = ids + (size_t)blockIdx.x * S;
+  int tmax = 0, tmin = S;  // the identities: token 0 starts a run, S - 1 ends one
+  for (int i = tid * 16; i < tid * 16 + 16 && i < S; ++i) {
+    const int id = row[i];
+    if (i > 0 && row[i - 1] != id) tmax = i;  // ascending: the last one stays
+    if (tmin == S && i + 1 < S && row[i + 1] != id) tmin = i + 1;
+  }
+  pmax[tid] = tmax;
+  smin[tid] = tmin;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int a = tid >= off ? pmax[tid - off] : 0;
+    const int c = tid + off < 256 ? smin[tid + off] : S;
+    __syncthreads();
+    pmax[tid] = pmax[tid] > a ? pmax[tid] : a;
+    smin[tid] = smin[tid] < c ? smin[tid] : c;
+    __syncthreads();
+  }
+  const int QB = (S + 63) / 64;
+  if (tid < QB) {
+    // block tid = tokens f..e, threads 4*tid..4*tid + 3
+    const int f = tid * 64;
+    const int e = f + 63 < S ? f + 63 : S - 1;
+    int lo = f, hi = e + 1;
+    if (f > 0 && row[f - 1] == row[f]) lo = pmax[4 * tid - 1];
+    if (e + 1 < S && row[e + 1] == row[e]) hi = smin[4 * tid + 4];
+    int* bd = bounds + ((size_t)blockIdx.x * QB + tid) * 2;
+    bd[0] = lo;
+    bd[1] = hi;
+  }
+}
+
+// ids: int32 [B][S]; bounds: int32 [B][ceil(S/64)][2], every element written
+SKY_EXPORT int sky_attn_seg_bounds(uint64_t stream, uint64_t ids,
+                                   uint64_t bounds, int64_t B, int64_t S) {
+  if (!atl_shape_ok(S, ATT_D) || ids == 0 || bounds == 0)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(attn_seg_bounds_kernel, dim3((unsigned)B), dim3(256), 0,
+                     (hipStream_t)stream, (const int*)ids, (int*)bounds, (int)S);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// The segment forms of sky_attn_long_fwd / sky_attn_long_bwd: ids in the
+// place of the additive mask, bounds from sky_attn_seg_bounds on the same ids.
+SKY_EXPORT int sky_attn_long_seg_fwd(uint64_t stream, uint64_t qkv,
+                                     uint64_t ids, uint64_t bounds,
+                                     uint64_t out, uint64_t m, uint64_t lsum,
+                                     int64_t B, int64_t S, int64_t h, int64_t d,
+                                     float scale, float keep, uint64_t salt,
+                                     uint64_t state) {
+  if (!atl_shape_ok(S, d) || ids == 0 || bounds == 0)
+    return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  hipLaunchKernelGGL((attn_fwd_long_kernel<false, true>), grid, dim3(256),
+                     ATL_FWD_LDS, (hipStream_t)stream, (const ushort_t*)qkv,
+                     (const ushort_t*)ids, (ushort_t*)out, (float*)m,
+                     (float*)lsum, (int)B, (int)S, (int)h, scale, keep, salt,
+                     (const unsigned long long*)state, (const int*)bounds);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_long_seg_bwd(uint64_t stream, uint64_t qkv,
+                                     uint64_t dout, uint64_t out, uint64_t ids,
+                                     uint64_t bounds, uint64_t m, uint64_t lsum,
+                                     uint64_t dot, uint64_t dqkv, int64_t B,
+                                     int64_t S, int64_t h, int64_t d,
+                                     float scale, float keep, uint64_t salt,
+                                     uint64_t state) {
+  if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || ids == 0 || bounds == 0)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, false, true>), grid,
+                     dim3(256), ATL_DQ_LDS, s, (const ushort_t*)qkv,
+                     (const ushort_t*)dout, (const ushort_t*)out,
+                     (const ushort_t*)ids, (const float*)m, (const float*)lsum,
+                     (float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
+                     keep, salt, (const unsigned long long*)state,
+                     (float*)nullptr, (const int*)bounds);
+  hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, false, true>), grid,
+                     dim3(256), ATL_DKV_SEG_LDS, s, (const ushort_t*)qkv,
+                     (const ushort_t*)dout, (const ushort_t*)ids,
+                     (const float*)m, (const float*)lsum, (const float*)dot,
+                     (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep, salt,
+                     (const unsigned long long*)state, (float*)nullptr,
+                     (const int*)bounds);
+  LAUNCH_CHECK();
+  return 0;
 }

@@ -129,6 +129,13 @@ def _register_signatures(lib):
         # sky_attn_long_bwd's arguments + scratch, dbias, dbias dt (as sky_attn_bwd_dbias)
         "sky_attn_long_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
         # sky_attn_long_bwd_dbias's arguments + job (host FinishJob*)
+        # packed sequences: int32 segment ids [B, S] in the place of the mask,
+        # bounds int32 [B, ceil(S/64), 2] from sky_attn_seg_bounds
+        "sky_attn_seg_bounds": [u64, u64, u64, i64, i64],  # strm ids bounds B S
+        "sky_attn_long_seg_fwd": [u64] * 7 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        # strm qkv ids bounds out m l | B S h d scale keep salt state
+        "sky_attn_long_seg_bwd": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        # strm qkv dout out ids bounds m l dot dqkv | B S h d scale keep salt state
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending

@@ -125,9 +125,17 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
     tail) whose tokens attend each other. GPU, bf16, d=64, 128 < S <= 4096:
     the segment form of the chunked kernels at every such S unless
     SKY_ATTN_LONG=0 (only the chunks a block's runs touch are visited; the
-    run rule is not checked there, a check would synchronise); other GPU
-    shapes: torch sdpa with the dense boolean mask; CPU: the eager path,
-    which raises ValueError for ids that break the run rule.
+    run rule is not checked there, a check would synchronise); 2 <= S <= 128:
+    the segment mode of the one-chunk kernels (a wave visits only the score
+    tiles of the key range its queries can see) where
+    functions.attn_seg_enabled selects it: SKY_ATTN_SEG_SHORT=1 / 0, unset
+    by the measurement of profiles/r15_notes.md, and never under
+    SKY_NO_FUSED_ATTN=1, SKY_NO_FUSED_ATTN_BWD=1 or SKY_ATTN_FUSED_BWD=1.
+    On the hand kernels packed attention draws its dropout mask from the
+    project's counter RNG (ARCHITECTURE section 4), not from torch's
+    generator. Other GPU shapes (S = 1 among them): torch sdpa with the
+    dense boolean mask; CPU: the eager path, which raises ValueError for ids
+    that break the run rule.
 
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
     (FusedAttentionFn); 128 < S <= 4096: its chunked form where
@@ -144,16 +152,13 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
             raise ValueError("attention: give either mask or segment_ids, not both")
         if segment_ids.shape != (B, S) or segment_ids.is_floating_point():
             raise ValueError("segment_ids must be an integer tensor [B, S]")
-        if (
-            qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64
-            and 128 < S <= 4096 and _use_hip(qkv)
-            and os.environ.get("SKY_ATTN_LONG") != "0"
-        ):
-            from .functions import FusedAttentionFn
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64:
+            from .functions import FusedAttentionFn, attn_seg_enabled
 
-            out = FusedAttentionFn.apply(qkv, None, scale, dropout_p, training,
-                                         segment_ids)
-            return out.reshape(B, S, h * d)
+            if attn_seg_enabled(S) and _use_hip(qkv):
+                out = FusedAttentionFn.apply(qkv, None, scale, dropout_p,
+                                             training, segment_ids)
+                return out.reshape(B, S, h * d)
         q, k, v = _split_heads(qkv)
         same = eager.segment_mask(segment_ids, check=not qkv.is_cuda)
         if qkv.is_cuda:
@@ -259,15 +264,22 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     LayerNorm width supported by the three-sum backward: one autograd node
     (AttentionBlockFn) whose backward takes the qkv dbias from the
     attention backward kernels and sums hidden's two gradients inside the
-    qkv dgrad GEMM. Everything else — CPU, fp32, long sequences,
+    qkv dgrad GEMM. segment_ids (packed sequences, in place of mask) take the
+    same node wherever ops.attention runs FusedAttentionFn on them
+    (functions.attn_seg_enabled), with the dropout mask of the project's
+    counter RNG. Everything else — CPU, fp32, long sequences,
     SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
-    paths, and segment_ids (packed sequences, see ops.attention) — is the
-    composition of ops.linear, ops.attention and
+    paths — is the composition of ops.linear, ops.attention and
     ops.linear_residual_layer_norm."""
     B, S, H = hidden.shape
     d = H // num_heads
+    # ids the node cannot take (next to a mask, wrong shape or type) go to
+    # ops.attention, which raises for them
+    ids_ok = segment_ids is None or (
+        mask is None and segment_ids.shape == (B, S)
+        and not segment_ids.is_floating_point())
     if (
-        segment_ids is None and hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
+        ids_ok and hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
         and qkv_bias is not None and out_bias is not None
         and hiplib.available()
         and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
@@ -276,18 +288,22 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     ):
         from .functions import (
             AttentionBlockFn, attn_block_enabled, attn_long_enabled,
-            ln_dbias_enabled, ln_xsum_width_ok,
+            attn_seg_enabled, ln_dbias_enabled, ln_xsum_width_ok,
         )
 
+        if segment_ids is not None:
+            fused = attn_seg_enabled(S)
+        else:
+            fused = S <= 128 or attn_long_enabled(S)
         if (
-            (S <= 128 or attn_long_enabled(S)) and attn_block_enabled()
+            fused and attn_block_enabled()
             and ln_dbias_enabled() and ln_xsum_width_ok(H)
         ):
             ap = attn_dropout_p if (training and attn_dropout_p > 0) else 0.0
             hp = hidden_dropout_p if training else 0.0
             return AttentionBlockFn.apply(
                 hidden, qkv_weight, qkv_bias, mask, num_heads, ap,
-                out_weight, out_bias, ln_weight, ln_bias, eps, hp
+                out_weight, out_bias, ln_weight, ln_bias, eps, hp, segment_ids
             )
     qkv = linear(hidden, qkv_weight, qkv_bias).view(B, S, 3, num_heads, d)
     attn = attention(qkv, mask, attn_dropout_p, training, segment_ids)

@@ -343,6 +343,34 @@ def attn_long_enabled(S: int) -> bool:
             and _ATTN_LONG_DEFAULT[0] < S <= _ATTN_LONG_DEFAULT[1])
 
 
+# SKY_ATTN_SEG_SHORT unset: whether packed attention at 2 <= S <= 128 runs the
+# segment mode of the one-chunk kernels. On: at B = 32, S = 128, h = 16 its
+# forward + backward median beat sdpa with the dense boolean mask with
+# non-overlapping ranges, 127 against 198 us (profiles/r15_notes.md).
+_ATTN_SEG_SHORT_DEFAULT = True
+
+
+def attn_seg_enabled(S: int) -> bool:
+    """Whether ops.attention / ops.attention_block run the hand kernels on
+    segment ids at this S. 2 <= S <= 128: SKY_ATTN_SEG_SHORT=1 / 0, unset by
+    measurement, and never under an env switch that selects another S <= 128
+    attention path; 128 < S <= 4096: unless SKY_ATTN_LONG=0. S = 1: never."""
+    if S > ATTN_SMAX:
+        return S <= ATTN_LONG_SMAX and os.environ.get("SKY_ATTN_LONG") != "0"
+    if S < 2 or any(os.environ.get(v) == "1" for v in (
+            "SKY_NO_FUSED_ATTN", "SKY_NO_FUSED_ATTN_BWD", "SKY_ATTN_FUSED_BWD")):
+        return False
+    e = os.environ.get("SKY_ATTN_SEG_SHORT")
+    return e == "1" if e in ("0", "1") else _ATTN_SEG_SHORT_DEFAULT
+
+
+def _attn_seg(segment_ids):
+    """Segment ids as the kernels take them: (int32 ids,) for S <= 128, where
+    the kernels find their ranges from the ids, (ids, bounds) above."""
+    ids = segment_ids.to(torch.int32).contiguous()
+    return (ids, attn_seg_bounds(ids)) if ids.shape[1] > ATTN_SMAX else (ids,)
+
+
 def attn_seg_bounds(ids):
     """sky_attn_seg_bounds on int32 segment ids [B, S], 128 < S <= 4096: per
     64-token block the run start of its first token and the run end of its
@@ -357,8 +385,8 @@ def attn_seg_bounds(ids):
 def _attn_fwd(qkv, mask, scale, keep, seg=None):
     """sky_attn_fwd (S <= 128) or sky_attn_long_fwd on a contiguous packed
     qkv [B, S, 3, h, 64]; draws the dropout salt when keep < 1. Returns
-    (out [B, S, h, d], m, lsum, salt). seg = (ids, bounds): the segment
-    form sky_attn_long_seg_fwd, S > 128 only."""
+    (out [B, S, h, d], m, lsum, salt). seg (_attn_seg): the segment form,
+    sky_attn_long_seg_fwd on (ids, bounds) or sky_attn_seg_fwd on (ids,)."""
     lib = hiplib.require()
     B, S, _, h, d = qkv.shape
     out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
@@ -367,7 +395,8 @@ def _attn_fwd(qkv, mask, scale, keep, seg=None):
     salt = _next_seed() if keep < 1.0 else 0
     state = rng_state()
     if seg is not None:
-        name, masks = "sky_attn_long_seg_fwd", (ptr(seg[0]), ptr(seg[1]))
+        name = "sky_attn_long_seg_fwd" if S > ATTN_SMAX else "sky_attn_seg_fwd"
+        masks = tuple(ptr(t) for t in seg)
     else:
         name = "sky_attn_long_fwd" if S > ATTN_SMAX else "sky_attn_fwd"
         masks = (ptr(mask),)
@@ -422,10 +451,13 @@ class FusedAttentionFn(torch.autograd.Function):
     recompute + hipBLASLt batched GEMMs + HIP softmax-backward).
 
     qkv: [B, S, 3, h, d] (d = 64), mask: [B, 1, 1, S] additive or None.
-    segment_ids (packed sequences, 128 < S <= 4096, no mask): integer
+    segment_ids (packed sequences, 2 <= S <= 4096, no mask): integer
     [B, S], q attends k iff their ids are equal; equal ids must form one
     contiguous run per row, which is NOT checked here (a check would
-    synchronise). The block bounds are computed once and saved for backward.
+    synchronise). The ids are converted to int32 once and saved; above
+    S = 128 the block bounds are computed once and saved with them, up to
+    S = 128 each wave finds its range from the ids (the segment mode of the
+    keys-on-rows kernels; the env switches of the backward do not apply).
     Returns [B, S, h, d].
     """
 
@@ -438,9 +470,8 @@ class FusedAttentionFn(torch.autograd.Function):
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
         seg = ()
         if segment_ids is not None:
-            assert mask is None and S > ATTN_SMAX and segment_ids.shape == (B, S)
-            ids = segment_ids.to(torch.int32).contiguous()
-            seg = (ids, attn_seg_bounds(ids))
+            assert mask is None and S >= 2 and segment_ids.shape == (B, S)
+            seg = _attn_seg(segment_ids)
         out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep, seg or None)
         # the long backward takes its row dots from dO * O
         extra = (out,) if S > ATTN_SMAX else ()
@@ -469,6 +500,21 @@ class FusedAttentionFn(torch.autograd.Function):
             else:
                 check(lib.sky_attn_long_bwd(*args), "sky_attn_long_bwd")
             return dqkv, None, None, None, None, None
+        if extra:
+            # (ids,): the segment mode of the keys-on-rows pair; its only
+            # scratch is the fp32 row dots, passed in pdT's place
+            dout = dout.contiguous()
+            dqkv = torch.empty_like(qkv)
+            dot = torch.empty(B * h * S, dtype=torch.float32, device=dev)
+            check(
+                lib.sky_attn_seg_bwd(
+                    _stream(), ptr(qkv), ptr(dout), ptr(extra[0]), ptr(m),
+                    ptr(lsum), ptr(dot), 0, ptr(dqkv), B, S, h, d, ctx.scale,
+                    ctx.keep, ctx.salt, rng_state().data_ptr(),
+                ),
+                "sky_attn_seg_bwd",
+            )
+            return dqkv, None, None, None, None, None
         if os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1":
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)
@@ -485,7 +531,7 @@ class FusedAttentionFn(torch.autograd.Function):
                     ),
                     "sky_attn_bwd_fused",
                 )
-                return dqkv, None, None, None, None
+                return dqkv, None, None, None, None, None
             # two-kernel path (bwd1s + bwd2 over transposed scratch)
             pdT, dsT = _attn_bwd_scratch(qkv)
             check(
@@ -497,7 +543,7 @@ class FusedAttentionFn(torch.autograd.Function):
                 ),
                 "sky_attn_bwd",
             )
-            return dqkv, None, None, None, None
+            return dqkv, None, None, None, None, None
         P = torch.empty(B, h, S, S, dtype=qkv.dtype, device=dev)
         Pd = torch.empty_like(P) if ctx.keep < 1.0 else P
         check(
@@ -519,7 +565,7 @@ class FusedAttentionFn(torch.autograd.Function):
             return dPd
 
         dqkv = _attn_bwd_decomposed(qkv, P, Pd, dout, ctx.scale, dP_of)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None
 
 
 class FlashAttentionFn(torch.autograd.Function):
@@ -978,11 +1024,15 @@ class AttentionBlockFn(torch.autograd.Function):
       * fold autograd's add of hidden's two gradients (residual branch and
         qkv linear) into the qkv dgrad GEMM (beta = 1 on dres).
     bf16, d = 64, S <= 4096 only (the fused attention kernels' domain; the
-    long kernels above S = 128); mask [B, 1, 1, S] additive or None."""
+    long kernels above S = 128); mask [B, 1, 1, S] additive or None.
+    segment_ids (packed sequences, S >= 2) in place of mask: integer [B, S]
+    as in FusedAttentionFn, whose segment forward this runs; the backward
+    takes the segment forms of the dbias entry points (the bounds table of
+    S > 128 is computed once in forward and saved)."""
 
     @staticmethod
     def forward(ctx, hidden, wqkv, bqkv, mask, num_heads, attn_p, wo, bo,
-                ln_w, ln_b, eps, hidden_p):
+                ln_w, ln_b, eps, hidden_p, segment_ids=None):
         B, S, H = hidden.shape
         d = H // num_heads
         assert d == 64 and S <= ATTN_LONG_SMAX and hidden.dtype == torch.bfloat16
@@ -992,13 +1042,17 @@ class AttentionBlockFn(torch.autograd.Function):
         mask = mask.contiguous() if mask is not None else None
         scale = 1.0 / math.sqrt(d)
         akeep = 1.0 - attn_p
-        ctxl, m, lsum, asalt = _attn_fwd(qkv, mask, scale, akeep)
+        seg = ()
+        if segment_ids is not None:
+            assert mask is None and S >= 2 and segment_ids.shape == (B, S)
+            seg = _attn_seg(segment_ids)
+        ctxl, m, lsum, asalt = _attn_fwd(qkv, mask, scale, akeep, seg or None)
         c2 = ctxl.view(-1, H)
         h = _linear_fwd(c2, wo, bo).view(B, S, H)
         keep = 1.0 - hidden_p
         y, mean, rstd, salt = _ln_fwd(h, hidden, ln_w, ln_b, eps, keep)
         ctx.save_for_backward(x2, wqkv, qkv, mask, m, lsum, c2, wo, h, ln_w,
-                              mean, rstd)
+                              mean, rstd, *seg)
         ctx.scale, ctx.akeep, ctx.asalt = scale, akeep, asalt
         ctx.keep, ctx.salt = keep, salt
         return y
@@ -1007,7 +1061,7 @@ class AttentionBlockFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = hiplib.require()
         (x2, wqkv, qkv, mask, m, lsum, c2, wo, h, ln_w, mean,
-         rstd) = ctx.saved_tensors
+         rstd, *seg) = ctx.saved_tensors
         B, S, _, nh, d = qkv.shape
         H = nh * d
         # the LN and dbqkv slab reductions finish in one launch, after the
@@ -1023,7 +1077,7 @@ class AttentionBlockFn(torch.autograd.Function):
         dbqkv = torch.empty(3 * H, dtype=wqkv.dtype, device=qkv.device)
         # the S <= 128 scratch first, then the slabs: the allocation order
         # this node has always had
-        if S > ATTN_SMAX:
+        if S > ATTN_SMAX or seg:
             scratch = (torch.empty(B * nh * S, dtype=torch.float32, device=qkv.device),)
         else:
             scratch = _attn_bwd_scratch(qkv)
@@ -1037,6 +1091,15 @@ class AttentionBlockFn(torch.autograd.Function):
             entry = "sky_attn_long_bwd_dbias"
             args = _attn_long_bwd_args(qkv, dctx, c2, mask, m, lsum, scratch[0],
                                        dqkv, ctx.scale, ctx.akeep, ctx.asalt)
+            if seg:  # (ids, bounds) in the mask's place
+                entry = "sky_attn_long_seg_bwd_dbias"
+                args = args[:4] + (ptr(seg[0]), ptr(seg[1])) + args[5:]
+        elif seg:
+            # (ids,) in the mask's place; the row dots are the only scratch
+            entry = "sky_attn_seg_bwd_dbias"
+            args = (_stream(), ptr(qkv), ptr(dctx), ptr(seg[0]), ptr(m),
+                    ptr(lsum), ptr(scratch[0]), 0, ptr(dqkv), B, S, nh, d,
+                    ctx.scale, ctx.akeep, ctx.asalt, rng_state().data_ptr())
         else:
             entry = "sky_attn_bwd_dbias"
             pdT, dsT = scratch
@@ -1065,7 +1128,7 @@ class AttentionBlockFn(torch.autograd.Function):
         if dbo.dtype != wo.dtype:
             dbo = dbo.to(wo.dtype)
         return (dres.view(B, S, H), dwqkv, dbqkv, None, None, None, dwo, dbo,
-                d_ln_w, d_ln_b, None, None)
+                d_ln_w, d_ln_b, None, None, None)
 
 
 def _linear_gelu_fwd(x2, weight, bias):

@@ -263,12 +263,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(
 //   * O^T leaves a lane with four consecutive d of its token: 8-byte stores.
 // One block per (b, h, 64*QPW-query block); a wave owns QPW 16-query tiles
 // 64 queries apart. LDS: K [128][64] sw7 @0, V @16K, key mask fp32 @32K.
+// SEG (packed sequences, QPW = 1): mask points at int32 segment ids [B][S],
+// which take the key mask's LDS slot; a lane compares its query's id with a
+// tile's four key ids (att_seg_mask4), and the wave visits only the score
+// tiles t0..t1 and contraction pairs p0..p1 that intersect the one key range
+// its 16 queries can see (att_seg_wave_range). A skipped tile's registers
+// keep att_zero's exact zeros, which is the P a packed pair wants from it.
+// K and V are staged whole: the range differs per wave, the images are the
+// block's. The diagonal is always in range, so the row max is a real score.
 #define KR_K_OFF KR_IMG0_OFF
 #define KR_V_OFF KR_IMG1_OFF
 #define KR_MASK_OFF KR_AUX_OFF
 #define KR_LDS_BYTES (KR_AUX_OFF + 512)
 
-template <bool HAS_MASK, int QPW>
+template <bool HAS_MASK, int QPW, bool SEG = false>
 __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
     ushort_t* __restrict__ out, float* __restrict__ m_io,
@@ -301,7 +309,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
   // values that the -3e38 mask (scores) and the zero P (PV) null
   att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KR_K_OFF, tid);
   att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KR_V_OFF, tid);
-  att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  static_assert(!SEG || (QPW == 1 && !HAS_MASK), "segment mode: QPW = 1, no mask");
+  if constexpr (SEG) att_seg_ids_lds((int*)mk, (const int*)mask, b, S, tid);
+  else att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -316,14 +326,27 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
       bq[ks] = *(const bf16x8*)(qbase + (size_t)qc * ts + ks * 32 + lg * 8);
+    // SEG: the lane's query id and the wave's key range, in tiles and pairs
+    int qid = 0, t0 = 0, t1 = NT, p0 = 0, p1 = NP;
+    if constexpr (SEG) {
+      const int* sk = (const int*)mk;
+      qid = sk[qc];  // lane 15 holds the wave's last valid query
+      int lo, hi;
+      att_seg_wave_range(lo, hi, sk, __builtin_amdgcn_readlane(qid, 0),
+                         __builtin_amdgcn_readlane(qid, 15), S, l);
+      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    }
     f32x4 sacc[8];
     att_zero(sacc);
-    att_score_tile_t(sacc, bq, lds, KR_K_OFF, NT, lm, lg);
+    if constexpr (SEG) att_score_tile_t_range(sacc, bq, lds, KR_K_OFF, t0, t1, lm, lg);
+    else att_score_tile_t(sacc, bq, lds, KR_K_OFF, NT, lm, lg);
     float mx = -3.0e38f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
-      const f32x4 mv = att_mask_keys4(mk, mt, lg);
+      if (mt < t0 || mt >= t1) continue;
+      f32x4 mv;
+      if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
+      else mv = att_mask_keys4(mk, mt, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float zz = sacc[mt][r] * scale + mv[r];
@@ -336,7 +359,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
     float sm = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
+      if (mt < t0 || mt >= t1) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = __expf(sacc[mt][r] - mx);
@@ -356,7 +379,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
     if (keep < 1.f) att_drop_hash_krows(z, seed, bh, S, q, lg);
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
+      if (mt < t0 || mt >= t1) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = sacc[mt][r] * inv;
@@ -369,7 +392,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
     att_zero(oacc);
 #pragma unroll
     for (int kp = 0; kp < 4; ++kp) {
-      if (kp >= NP) continue;
+      if (kp < p0 || kp >= p1) continue;
       const bf16x8 bp = att_pack_dpair(sacc[2 * kp], sacc[2 * kp + 1]);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
@@ -488,6 +511,28 @@ SKY_EXPORT int sky_attn_fwd(uint64_t stream, uint64_t qkv, uint64_t mask,
                             uint64_t state) {
   return attn_launch(stream, qkv, mask, out, m, lsum, 0, 0, B, S, h, d,
                      scale, keep, salt, state, false);
+}
+
+// The segment form of sky_attn_fwd (packed sequences): ids, int32 [B][S], in
+// the mask's place; q attends k iff their ids are equal, and equal ids form
+// one contiguous run per row. 2 <= S <= 128 (the backward's dot hand-off
+// needs S >= 2), d = 64. Always the keys-on-rows kernel: the older generation
+// has no segment form and SKY_ATTN_KROWS does not apply.
+SKY_EXPORT int sky_attn_seg_fwd(uint64_t stream, uint64_t qkv, uint64_t ids,
+                                uint64_t out, uint64_t m, uint64_t lsum,
+                                int64_t B, int64_t S, int64_t h, int64_t d,
+                                float scale, float keep, uint64_t salt,
+                                uint64_t state) {
+  if (d != ATT_D || S < 2 || S > ATT_SMAX || ids == 0)
+    return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  hipLaunchKernelGGL((attn_fwd_krows_kernel<false, 1, true>), grid, dim3(256),
+                     KR_LDS_BYTES, (hipStream_t)stream, (const ushort_t*)qkv,
+                     (const ushort_t*)ids, (ushort_t*)out, (float*)m,
+                     (float*)lsum, (int)B, (int)S, (int)h, scale, keep, salt,
+                     (const unsigned long long*)state);
+  LAUNCH_CHECK();
+  return 0;
 }
 
 SKY_EXPORT int sky_attn_probs(uint64_t stream, uint64_t qkv, uint64_t mask,

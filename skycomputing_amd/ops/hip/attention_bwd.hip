@@ -569,13 +569,21 @@ SKY_EXPORT int sky_attn_bwd_fused(uint64_t stream, uint64_t qkv,
 // writes dot[bh*S + q] (fp32) for the second kernel, and with DBIAS the
 // block's 64 dQ column sums to slab b*QB + qb like attn_bwd1s_kernel.
 // LDS: K [128][64] sw7 @0, V @16K, key mask fp32 @32K, DBIAS sums @32.5K.
+//
+// SEG (packed sequences) in both kernels, as in attn_fwd_krows_kernel: mask
+// points at int32 segment ids [B][S]; a pair of another segment gets the
+// additive -3e38, so P, rebuilt from the saved m and 1/l, is exp(-huge) = 0
+// and dS with it. A wave visits only the 16-token tiles and 32-token
+// contraction pairs of the one range its 16 tokens can see
+// (att_seg_wave_range); a skipped tile inside a visited pair keeps exact
+// zeros in its P / dS registers. The images are staged whole.
 #define KRB_K_OFF KR_IMG0_OFF
 #define KRB_V_OFF KR_IMG1_OFF
 #define KRB_MASK_OFF KR_AUX_OFF
 #define KRB_SUM_OFF (KR_AUX_OFF + 512)
 #define KRB_DQ_LDS (KR_AUX_OFF + 512 + 1024)
 
-template <bool HAS_MASK, bool DBIAS>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
@@ -615,7 +623,9 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
 
   att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KRB_K_OFF, tid);
   att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KRB_V_OFF, tid);
-  att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  static_assert(!SEG || !HAS_MASK, "segment mode takes ids in the mask's place");
+  if constexpr (SEG) att_seg_ids_lds((int*)mk, (const int*)mask, b, S, tid);
+  else att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
   bf16x8 bq[2], bdo[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
@@ -629,19 +639,36 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
 
   float cs = 0.f;
   if (active) {
+    // SEG: the lane's query id and the wave's key range, in tiles and pairs
+    int qid = 0, t0 = 0, t1 = NT, p0 = 0, p1 = NP;
+    if constexpr (SEG) {
+      const int* sk = (const int*)mk;
+      qid = sk[qc];  // lane 15 holds the wave's last valid query
+      int lo, hi;
+      att_seg_wave_range(lo, hi, sk, __builtin_amdgcn_readlane(qid, 0),
+                         __builtin_amdgcn_readlane(qid, 15), S, l);
+      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    }
     f32x4 sacc[8], dacc[8];
     att_zero(sacc);
     att_zero(dacc);
-    att_score_tile_t(sacc, bq, lds, KRB_K_OFF, NT, lm, lg);   // K Q^T
-    att_score_tile_t(dacc, bdo, lds, KRB_V_OFF, NT, lm, lg);  // V dO^T
+    if constexpr (SEG) {
+      att_score_tile_t_range(sacc, bq, lds, KRB_K_OFF, t0, t1, lm, lg);
+      att_score_tile_t_range(dacc, bdo, lds, KRB_V_OFF, t0, t1, lm, lg);
+    } else {
+      att_score_tile_t(sacc, bq, lds, KRB_K_OFF, NT, lm, lg);   // K Q^T
+      att_score_tile_t(dacc, bdo, lds, KRB_V_OFF, NT, lm, lg);  // V dO^T
+    }
     uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     if (keep < 1.f) att_drop_hash_krows(z, seed, bh, S, q, lg);
     // P -> sacc, dropout-masked dP -> dacc, row dot
     float dot = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
-      const f32x4 mv = att_mask_keys4(mk, mt, lg);
+      if (mt < t0 || mt >= t1) continue;
+      f32x4 mv;
+      if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
+      else mv = att_mask_keys4(mk, mt, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = mt * 16 + lg * 4 + r;
@@ -663,7 +690,8 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
     att_zero(qacc);
 #pragma unroll
     for (int kp = 0; kp < 4; ++kp) {
-      if (kp >= NP) continue;
+      if (kp < p0 || kp >= p1) continue;
+      // (a skipped tile of a visited pair: P = dP = 0, so dS = 0 exactly)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -710,8 +738,12 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
 #define KRB_BITS_OFF (KR_AUX_OFF + 1536)
 #define KRB_SUM2_OFF (KR_AUX_OFF + 1536 + 2048)
 #define KRB_DKV_LDS (KR_AUX_OFF + 1536 + 2048 + 2048)
+// SEG: the row's query ids, int32 [128], one more word array @37.5K; the
+// lane's key id in a register, the wave's QUERY range from the ids
+#define KRB_QID_OFF KRB_DKV_LDS
+#define KRB_DKV_SEG_LDS (KRB_DKV_LDS + 512)
 
-template <bool HAS_MASK, bool DBIAS>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
@@ -770,24 +802,39 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
   float mv = 0.f;
   if (HAS_MASK && key < S) mv = bf16_to_f32(mask[(size_t)b * S + key]);
   if (key >= S) mv = -3.0e38f;
+  static_assert(!SEG || !HAS_MASK, "segment mode takes ids in the mask's place");
+  const int* sq = (const int*)lds_at(lds, KRB_QID_OFF);
+  int kid = 0;
+  if constexpr (SEG) {
+    att_seg_ids_lds((int*)lds_at(lds, KRB_QID_OFF), (const int*)mask, b, S, tid);
+    kid = ((const int*)mask)[(size_t)b * S + kc];  // lane 15: the last valid key
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   float ck = 0.f, cv = 0.f;
   if (active) {
+    // SEG: the wave's query range, in tiles and pairs
+    int t0 = 0, t1 = NT, p0 = 0, p1 = NP;
+    if constexpr (SEG) {
+      int lo, hi;
+      att_seg_wave_range(lo, hi, sq, __builtin_amdgcn_readlane(kid, 0),
+                         __builtin_amdgcn_readlane(kid, 15), S, l);
+      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    }
     f32x4 kacc[4], vacc[4];
     att_zero(kacc);
     att_zero(vacc);
 #pragma unroll
     for (int qp = 0; qp < 4; ++qp) {
-      if (qp >= NP) continue;
+      if (qp < p0 || qp >= p1) continue;
       f32x4 pd[2], ds[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int qt = 2 * qp + t;
         pd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         ds[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (qt >= NT) continue;
+        if (qt < t0 || qt >= t1) continue;
         const int qrow = qt * 16 + lm;  // < NP*32: a staged (clamped) row
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -805,10 +852,13 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
         unsigned kbits = 0xFFFFFFFFu;
         if (keep < 1.f)
           kbits = *(const unsigned*)(bits + ((qt * 4 + lg) * 16 + lm) * 4);
+        att_i32x4 qid4 = {0, 0, 0, 0};
+        if constexpr (SEG) qid4 = *(const att_i32x4*)(sq + qt * 16 + lg * 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = qt * 16 + lg * 4 + r;
-          const float p = att_prob(s4[r], scale, mv, m4[r], il4[r],
+          const float mvr = (SEG && qid4[r] != kid) ? -3.0e38f : mv;
+          const float p = att_prob(s4[r], scale, mvr, m4[r], il4[r],
                                    qq < S && key < S);
           const bool kbit = (kbits >> (8 * r + w)) & 1u;
           float pdv = p, dp = d4[r];
@@ -859,7 +909,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
 // the default pair: dQ + dot, then dK/dV. dot (fp32 [B*h*S]) lives at the
 // head of the pdT scratch the entry points receive (2*S*S bytes per (b,h)
 // cover 4*S for S >= 2); nothing else of pdT / dsT is touched.
-template <bool DBIAS>
+template <bool DBIAS, bool SEG = false>
 static void launch_attn_bwd_krows(hipStream_t s, uint64_t qkv, uint64_t dout,
                                   uint64_t mask, uint64_t m, uint64_t lsum,
                                   uint64_t pdT, uint64_t dqkv, int64_t B,
@@ -867,6 +917,21 @@ static void launch_attn_bwd_krows(hipStream_t s, uint64_t qkv, uint64_t dout,
                                   float keep, uint64_t salt, uint64_t state,
                                   float* dbscr) {
   dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  if constexpr (SEG) {  // mask: the int32 segment ids
+    hipLaunchKernelGGL((attn_bwd_dq_krows_kernel<false, DBIAS, true>), grid,
+                       dim3(256), KRB_DQ_LDS, s, (const ushort_t*)qkv,
+                       (const ushort_t*)dout, (const ushort_t*)mask,
+                       (const float*)m, (const float*)lsum, (float*)pdT,
+                       (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep,
+                       salt, (const unsigned long long*)state, dbscr);
+    hipLaunchKernelGGL((attn_bwd_dkv_krows_kernel<false, DBIAS, true>), grid,
+                       dim3(256), KRB_DKV_SEG_LDS, s, (const ushort_t*)qkv,
+                       (const ushort_t*)dout, (const ushort_t*)mask,
+                       (const float*)m, (const float*)lsum, (const float*)pdT,
+                       (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep,
+                       salt, (const unsigned long long*)state, dbscr);
+    return;
+  }
   ATT_LAUNCH_HM(mask != 0, (attn_bwd_dq_krows_kernel<HM, DBIAS>), grid,
                 KRB_DQ_LDS, s, (const ushort_t*)qkv, (const ushort_t*)dout,
                 (const ushort_t*)mask, (const float*)m, (const float*)lsum,
@@ -941,11 +1006,15 @@ static int attn_bwd_dbias_impl(uint64_t stream, uint64_t qkv, uint64_t dout,
                                float scale, float keep, uint64_t salt,
                                uint64_t state, uint64_t scratch,
                                uint64_t dbias, int dbias_dt,
-                               SkyFinishJob* job) {
+                               SkyFinishJob* job, bool seg = false) {
   if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  if (attn_bwd_use_krows(S))
+  if (seg)  // mask: the segment ids; the caller has checked the shape
+    launch_attn_bwd_krows<true, true>(s, qkv, dout, mask, m, lsum, pdT, dqkv, B,
+                                      S, h, scale, keep, salt, state,
+                                      (float*)scratch);
+  else if (attn_bwd_use_krows(S))
     launch_attn_bwd_krows<true>(s, qkv, dout, mask, m, lsum, pdT, dqkv, B, S, h,
                                 scale, keep, salt, state, (float*)scratch);
   else
@@ -987,4 +1056,52 @@ SKY_EXPORT int sky_attn_bwd_dbias_parts(
   return attn_bwd_dbias_impl(stream, qkv, dout, mask, m, lsum, pdT, dsT, dqkv,
                              B, S, h, d, scale, keep, salt, state, scratch,
                              dbias, dbias_dt, (SkyFinishJob*)job);
+}
+
+// The segment forms (packed sequences) of the three entry points above: ids,
+// int32 [B][S], in the mask's place, after sky_attn_seg_fwd on the same ids.
+// 2 <= S <= 128 and d = 64; always the keys-on-rows pair (SKY_ATTN_KROWS does
+// not apply), so only the fp32 row dots at the head of pdT are written and
+// dsT is not touched.
+static bool attn_seg_shape_ok(int64_t S, int64_t d, uint64_t ids, uint64_t pdT) {
+  return d == ATT_D && S >= 2 && S <= ATT_SMAX && ids != 0 && pdT != 0;
+}
+
+SKY_EXPORT int sky_attn_seg_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
+                                uint64_t ids, uint64_t m, uint64_t lsum,
+                                uint64_t pdT, uint64_t dsT, uint64_t dqkv,
+                                int64_t B, int64_t S, int64_t h, int64_t d,
+                                float scale, float keep, uint64_t salt,
+                                uint64_t state) {
+  if (!attn_seg_shape_ok(S, d, ids, pdT)) return (int)hipErrorInvalidValue;
+  launch_attn_bwd_krows<false, true>((hipStream_t)stream, qkv, dout, ids, m,
+                                     lsum, pdT, dqkv, B, S, h, scale, keep,
+                                     salt, state, nullptr);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_seg_bwd_dbias(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t ids, uint64_t m,
+    uint64_t lsum, uint64_t pdT, uint64_t dsT, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt) {
+  if (!attn_seg_shape_ok(S, d, ids, pdT)) return (int)hipErrorInvalidValue;
+  return attn_bwd_dbias_impl(stream, qkv, dout, ids, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, nullptr, true);
+}
+
+SKY_EXPORT int sky_attn_seg_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t ids, uint64_t m,
+    uint64_t lsum, uint64_t pdT, uint64_t dsT, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt,
+    uint64_t job) {
+  if (job == 0 || !attn_seg_shape_ok(S, d, ids, pdT))
+    return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_bwd_dbias_impl(stream, qkv, dout, ids, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, (SkyFinishJob*)job, true);
 }

@@ -805,6 +805,32 @@ SKY_EXPORT int sky_attn_long_seg_fwd(uint64_t stream, uint64_t qkv,
   return 0;
 }
 
+// the segment pair: dQ + dot, then dK/dV; DBIAS also fills the slabs
+template <bool DBIAS>
+static void launch_attn_long_seg_bwd(hipStream_t s, uint64_t qkv, uint64_t dout,
+                                     uint64_t out, uint64_t ids, uint64_t bounds,
+                                     uint64_t m, uint64_t lsum, uint64_t dot,
+                                     uint64_t dqkv, int64_t B, int64_t S,
+                                     int64_t h, float scale, float keep,
+                                     uint64_t salt, uint64_t state,
+                                     float* dbscr) {
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+  hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, DBIAS, true>), grid,
+                     dim3(256), ATL_DQ_LDS, s, (const ushort_t*)qkv,
+                     (const ushort_t*)dout, (const ushort_t*)out,
+                     (const ushort_t*)ids, (const float*)m, (const float*)lsum,
+                     (float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
+                     keep, salt, (const unsigned long long*)state, dbscr,
+                     (const int*)bounds);
+  hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, DBIAS, true>), grid,
+                     dim3(256), ATL_DKV_SEG_LDS, s, (const ushort_t*)qkv,
+                     (const ushort_t*)dout, (const ushort_t*)ids,
+                     (const float*)m, (const float*)lsum, (const float*)dot,
+                     (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep, salt,
+                     (const unsigned long long*)state, dbscr,
+                     (const int*)bounds);
+}
+
 SKY_EXPORT int sky_attn_long_seg_bwd(uint64_t stream, uint64_t qkv,
                                      uint64_t dout, uint64_t out, uint64_t ids,
                                      uint64_t bounds, uint64_t m, uint64_t lsum,
@@ -814,22 +840,60 @@ SKY_EXPORT int sky_attn_long_seg_bwd(uint64_t stream, uint64_t qkv,
                                      uint64_t state) {
   if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || ids == 0 || bounds == 0)
     return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
-  hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, false, true>), grid,
-                     dim3(256), ATL_DQ_LDS, s, (const ushort_t*)qkv,
-                     (const ushort_t*)dout, (const ushort_t*)out,
-                     (const ushort_t*)ids, (const float*)m, (const float*)lsum,
-                     (float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
-                     keep, salt, (const unsigned long long*)state,
-                     (float*)nullptr, (const int*)bounds);
-  hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, false, true>), grid,
-                     dim3(256), ATL_DKV_SEG_LDS, s, (const ushort_t*)qkv,
-                     (const ushort_t*)dout, (const ushort_t*)ids,
-                     (const float*)m, (const float*)lsum, (const float*)dot,
-                     (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep, salt,
-                     (const unsigned long long*)state, (float*)nullptr,
-                     (const int*)bounds);
+  launch_attn_long_seg_bwd<false>((hipStream_t)stream, qkv, dout, out, ids,
+                                  bounds, m, lsum, dot, dqkv, B, S, h, scale,
+                                  keep, salt, state, nullptr);
   LAUNCH_CHECK();
   return 0;
+}
+
+// sky_attn_long_seg_bwd that also returns dbias[3*h*64]: the segment forms of
+// sky_attn_long_bwd_dbias / _parts, scratch and job as there
+static int attn_long_seg_bwd_dbias_impl(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t ids,
+    uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
+    int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
+    uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
+    int dbias_dt, SkyFinishJob* job) {
+  if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || ids == 0 || bounds == 0 ||
+      scratch == 0 || dbias == 0)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  launch_attn_long_seg_bwd<true>(s, qkv, dout, out, ids, bounds, m, lsum, dot,
+                                 dqkv, B, S, h, scale, keep, salt, state,
+                                 (float*)scratch);
+  const int64_t cols = 3 * h * ATT_D, nslabs = B * ((S + 63) / 64);
+  if (job)
+    sky_finish_job_set(job, scratch, dbias, 0, 0, nslabs, cols, 1, dbias_dt);
+  else
+    sky_launch_colsum_final(s, (const float*)scratch, (void*)dbias, cols,
+                            nslabs, dbias_dt);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_long_seg_bwd_dbias(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t ids,
+    uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
+    int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
+    uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
+    int dbias_dt) {
+  return attn_long_seg_bwd_dbias_impl(stream, qkv, dout, out, ids, bounds, m,
+                                      lsum, dot, dqkv, B, S, h, d, scale, keep,
+                                      salt, state, scratch, dbias, dbias_dt,
+                                      nullptr);
+}
+
+SKY_EXPORT int sky_attn_long_seg_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t ids,
+    uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
+    int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
+    uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
+    int dbias_dt, uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_long_seg_bwd_dbias_impl(stream, qkv, dout, out, ids, bounds, m,
+                                      lsum, dot, dqkv, B, S, h, d, scale, keep,
+                                      salt, state, scratch, dbias, dbias_dt,
+                                      (SkyFinishJob*)job);
 }

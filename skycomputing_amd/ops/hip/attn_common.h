@@ -194,6 +194,64 @@ DEV void att_mask_keys_lds_at(float* mk, bool has_mask,
   }
 }
 
+// ---- segment mode of the S <= 128 keys-on-rows kernels (packed sequences) ----
+// The row's int32 segment ids [B][S] take the LDS slot of the fp32 key mask,
+// written by threads 0..127 before the staging barrier; positions >= S repeat
+// id S-1 (att_seg_mask4 and att_seg_wave_range null them by position).
+typedef __attribute__((ext_vector_type(4))) int att_i32x4;
+
+DEV void att_seg_ids_lds(int* sk, const int* __restrict__ ids, int b, int S,
+                         int tid) {
+  if (tid < ATT_SMAX) sk[tid] = ids[(size_t)b * S + (tid < S ? tid : S - 1)];
+}
+// the additive values of tile mt's four tokens lg*4.. against the lane's own
+// id: 0 for the same segment, -3e38 (the value of a token >= S) otherwise
+DEV f32x4 att_seg_mask4(const int* sk, int mt, int lg, int own, int S) {
+  const att_i32x4 id = *(const att_i32x4*)(sk + mt * 16 + lg * 4);
+  f32x4 mv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    mv[r] = (id[r] == own && mt * 16 + lg * 4 + r < S) ? 0.f : -3.0e38f;
+  return mv;
+}
+// Equal ids form one contiguous run, so the tokens on the other side that a
+// wave's 16 tokens can see are ONE range [lo, hi): from the first token that
+// carries the id of the wave's first token (idf) to the last one that carries
+// the id of its last valid token (idl). Four 64-lane ballots over the 128 ids
+// in LDS; every lane of the wave must be here, and the results are wave
+// uniform. 0 <= lo < hi <= S for any ids (the wave's own tokens match
+// themselves; with no match at all the range is the whole row), so ids that
+// break the run rule cannot move an access: the range only selects tiles of
+// LDS images that were staged whole.
+DEV void att_seg_wave_range(int& lo, int& hi, const int* sk, int idf, int idl,
+                            int S, int l) {
+  const int a = sk[l], c = sk[64 + l];
+  const bool va = l < S, vc = 64 + l < S;
+  const unsigned long long f0 = __ballot(va && a == idf);
+  const unsigned long long f1 = __ballot(vc && c == idf);
+  const unsigned long long l0 = __ballot(va && a == idl);
+  const unsigned long long l1 = __ballot(vc && c == idl);
+  lo = f0 ? __builtin_ctzll(f0) : (f1 ? 64 + __builtin_ctzll(f1) : 0);
+  hi = l1 ? 128 - __builtin_clzll(l1) : (l0 ? 64 - __builtin_clzll(l0) : S);
+}
+// att_score_tile_t over the 16-token tiles t0 <= mt < t1 only; the other
+// accumulators keep what they hold (the callers' zeros)
+DEV void att_score_tile_t_range(f32x4 (&acc)[8], const bf16x8 (&b)[2],
+                                char* lds, int off, int t0, int t1, int lm,
+                                int lg) {
+#pragma unroll
+  for (int mt = 0; mt < 8; ++mt) {
+    if (mt < t0 || mt >= t1) continue;
+    const int tok = mt * 16 + lm;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 at = *(const bf16x8*)lds_at(
+          lds, swz(off + tok * 128 + (ks * 32 + lg * 8) * 2, tok, 7));
+      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at, b[ks], acc[mt], 0, 0, 0);
+    }
+  }
+}
+
 // stage nrows rows of a [tok][64] bf16 row image (token stride tstride,
 // first token tok0) to LDS offset off via global_load_lds. The XOR swizzle
 // moves to the SOURCE address (lane-linear LDS image == sw7 layout). With

@@ -136,6 +136,16 @@ def _register_signatures(lib):
         # strm qkv ids bounds out m l | B S h d scale keep salt state
         "sky_attn_long_seg_bwd": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout out ids bounds m l dot dqkv | B S h d scale keep salt state
+        "sky_attn_long_seg_bwd_dbias": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        "sky_attn_long_seg_bwd_dbias_parts": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        # sky_attn_long_seg_bwd's arguments + scratch, dbias, dbias dt (+ job)
+        # 2 <= S <= 128: the segment forms of sky_attn_fwd / sky_attn_bwd* (the
+        # keys-on-rows kernels), ids in the mask's place, no bounds table; only
+        # the fp32 row dots [B*h*S] at the head of pdT are written, dsT may be 0
+        "sky_attn_seg_fwd": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_seg_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_seg_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        "sky_attn_seg_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending

@@ -12,6 +12,7 @@ from .bert_layers import (
     SkyLayerNorm,
     bert_pipeline_config,
     bert_pretraining_pipeline_config,
+    causal_lm_pipeline_config,
 )
 from .resnet import ResHead, ResLayer, ResTail, resnet_pipeline_config
 
@@ -20,5 +21,6 @@ __all__ = [
     "BertLayerTail", "BertLMHead", "BertPooler", "BertTailForClassification",
     "BertSelfAttention", "LinearActivation", "SkyLayerNorm",
     "bert_pipeline_config", "bert_pretraining_pipeline_config",
+    "causal_lm_pipeline_config",
     "ResHead", "ResLayer", "ResTail", "resnet_pipeline_config",
 ]

@@ -26,6 +26,7 @@ class BertConfig:
         initializer_range: float = 0.02,
         layer_norm_eps: float = 1e-12,
         output_all_encoded_layers: bool = False,
+        causal: bool = False,
     ):
         if isinstance(vocab_size_or_config_json_file, str):
             with open(vocab_size_or_config_json_file) as f:
@@ -46,6 +47,8 @@ class BertConfig:
         self.initializer_range = initializer_range
         self.layer_norm_eps = layer_norm_eps
         self.output_all_encoded_layers = output_all_encoded_layers
+        # decoder-only (GPT-style) stacks: every attention layer is causal
+        self.causal = causal
 
     @classmethod
     def from_dict(cls, d: dict) -> "BertConfig":

@@ -113,11 +113,27 @@ class BertSelfAttention(nn.Module):
         H = config.hidden_size
         self.qkv = SkyLinear(H, 3 * H)
         self.dropout_p = config.attention_probs_dropout_prob
+        self.causal = bool(getattr(config, "causal", False))
 
     def forward(self, hidden, ext_mask):
         B, S, H = hidden.shape
         qkv = self.qkv(hidden).view(B, S, 3, self.num_heads, self.head_dim)
-        return ops.attention(qkv, ext_mask, self.dropout_p, self.training)
+        mask, ids = _causal_masks(ext_mask, self.causal)
+        return ops.attention(qkv, mask, self.dropout_p, self.training, ids, self.causal)
+
+
+def _causal_masks(ext_mask, causal: bool):
+    """(mask, segment_ids) for ops.attention / ops.attention_block from the
+    ext_mask slot: an integer ext_mask is BertEmbeddings' packed-sequence
+    segment ids. Under config key causal a floating (padding) ext_mask is NOT
+    given to the attention: batches must be right-padded, so that a real
+    query, which sees only keys at or before itself, never sees a pad key;
+    the pad positions themselves produce finite values that the loss must
+    ignore (ignore_index at those targets)."""
+    packed = ext_mask is not None and not ext_mask.is_floating_point()
+    if packed:
+        return None, ext_mask
+    return (None if causal else ext_mask), None
 
 
 class BertSelfOutput(nn.Module):
@@ -213,13 +229,14 @@ class BertLayerHead(nn.Module):
         # (what self.output(self.attention(hidden, ext_mask), hidden)
         # computes): on GPU a single autograd node, see ops.attention_block
         att, out = self.attention, self.output
-        # an integer ext_mask is BertEmbeddings' packed-sequence segment ids
-        packed = ext_mask is not None and not ext_mask.is_floating_point()
+        # an integer ext_mask is BertEmbeddings' packed-sequence segment ids;
+        # config key causal: no padding mask (_causal_masks)
+        mask, ids = _causal_masks(ext_mask, att.causal)
         y = ops.attention_block(
-            hidden, None if packed else ext_mask, att.qkv.weight,
+            hidden, mask, att.qkv.weight,
             att.qkv.bias, att.num_heads, att.dropout_p, out.dense.weight, out.dense.bias,
             out.layer_norm.weight, out.layer_norm.bias, out.layer_norm.eps,
-            out.dropout_p, self.training, ext_mask if packed else None)
+            out.dropout_p, self.training, ids, att.causal)
         return y, ext_mask
 
     def layer_flops(self, batch: int, seq: int) -> float:
@@ -407,6 +424,19 @@ def bert_pretraining_pipeline_config(
         layers.append(dict(layer_type="BertLayer_Tail", config=bc))
     layers.append(dict(layer_type="BertLMHead", config=bc))
     return layers
+
+
+def causal_lm_pipeline_config(
+    num_encoder_layers: int,
+    bert_config: dict | None = None,
+) -> list[dict]:
+    """The layer-config list of an N-layer decoder-only language model: the
+    pretraining list with causal=True in every layer's config (post-LN, GELU,
+    learned positions: the original GPT layout), ending in BertLMHead. Train
+    it with the "CausalLM" loss (optim.LOSSES) on right-padded or packed
+    batches."""
+    return bert_pretraining_pipeline_config(
+        num_encoder_layers, dict(bert_config or {}, causal=True))
 
 
 def bert_pipeline_config(

@@ -113,8 +113,48 @@ def attention_context(q, k, v, mask, dropout_p: float = 0.0, training: bool = Fa
     return eager.attention_context(q, k, v, mask, dropout_p, training)
 
 
+def _attention_causal(qkv, mask, dropout_p, training, segment_ids):
+    """ops.attention with causal=True at S >= 2 (see there)."""
+    from .functions import _split_heads
+
+    B, S, _, h, d = qkv.shape
+    if segment_ids is not None:
+        if mask is not None:
+            raise ValueError("attention: give either mask or segment_ids, not both")
+        if segment_ids.shape != (B, S) or segment_ids.is_floating_point():
+            raise ValueError("segment_ids must be an integer tensor [B, S]")
+    if mask is None and qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64:
+        from .functions import FusedAttentionFn, attn_causal_enabled
+
+        if attn_causal_enabled(S) and _use_hip(qkv):
+            out = FusedAttentionFn.apply(qkv, None, 1.0 / math.sqrt(d), dropout_p,
+                                         training, segment_ids, True)
+            return out.reshape(B, S, h * d)
+    q, k, v = _split_heads(qkv)
+    sdpa = torch.nn.functional.scaled_dot_product_attention
+    p = dropout_p if training else 0.0
+    if qkv.is_cuda and mask is None and segment_ids is None:
+        ctx = sdpa(q, k, v, is_causal=True, dropout_p=p)
+    else:
+        vis = eager.causal_mask(S, qkv.device)
+        if segment_ids is not None:
+            vis = vis & eager.segment_mask(segment_ids, check=not qkv.is_cuda)
+        if qkv.is_cuda and mask is None:
+            ctx = sdpa(q, k, v, attn_mask=vis, dropout_p=p)
+        else:
+            dense = torch.zeros(vis.shape, dtype=qkv.dtype,
+                                device=qkv.device).masked_fill_(~vis, float("-inf"))
+            if mask is not None:
+                dense = dense + mask.to(qkv.dtype)  # additive [B,1,1,S]
+            if qkv.is_cuda:
+                ctx = sdpa(q, k, v, attn_mask=dense, dropout_p=p)
+            else:
+                ctx = eager.attention_context(q, k, v, dense, dropout_p, training)
+    return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
+
+
 def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
-              segment_ids=None):
+              segment_ids=None, causal: bool = False):
     """Multi-head attention over a packed qkv tensor [B, S, 3, h, d];
     returns [B, S, h*d].
 
@@ -137,6 +177,19 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
     dense boolean mask; CPU: the eager path, which raises ValueError for ids
     that break the run rule.
 
+    causal: query q attends key k iff k <= q, and with segment_ids iff the
+    two ids are equal as well. GPU, bf16, d=64, 2 <= S <= 4096, no mask: the
+    triangle mode of the same hand kernels (tiles and chunks past the
+    diagonal are skipped) where functions.attn_causal_enabled selects it:
+    SKY_ATTN_CAUSAL=1 / 0, unset by the measurement of
+    profiles/r16_notes.md; never under SKY_NO_FUSED_ATTN=1,
+    SKY_NO_FUSED_ATTN_BWD=1 or SKY_ATTN_FUSED_BWD=1, nor above S = 128 under
+    SKY_ATTN_LONG=0. Elsewhere on the GPU: torch sdpa, is_causal=True with
+    neither ids nor mask, else the dense boolean or additive mask combined
+    with the lower triangle; CPU: the eager path on the dense additive mask.
+    An additive mask next to causal is never served by the hand kernels. At
+    S = 1 causal is the identity and the call takes the path it takes without.
+
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
     (FusedAttentionFn); 128 < S <= 4096: its chunked form where
     functions.attn_long_enabled selects it (256 <= S <= 512 by default,
@@ -147,6 +200,8 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
 
     B, S, three, h, d = qkv.shape
     scale = 1.0 / math.sqrt(d)
+    if causal and S > 1:
+        return _attention_causal(qkv, mask, dropout_p, training, segment_ids)
     if segment_ids is not None:
         if mask is not None:
             raise ValueError("attention: give either mask or segment_ids, not both")
@@ -254,7 +309,8 @@ def linear_residual_layer_norm(x, weight, bias, ln_weight, ln_bias,
 def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
                     attn_dropout_p: float, out_weight, out_bias, ln_weight,
                     ln_bias, eps: float = 1e-12, hidden_dropout_p: float = 0.0,
-                    training: bool = False, segment_ids=None):
+                    training: bool = False, segment_ids=None,
+                    causal: bool = False):
     """The attention third of an encoder block:
     LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
     for hidden [B, S, H], mask [B, 1, 1, S] additive or None.
@@ -267,19 +323,23 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     qkv dgrad GEMM. segment_ids (packed sequences, in place of mask) take the
     same node wherever ops.attention runs FusedAttentionFn on them
     (functions.attn_seg_enabled), with the dropout mask of the project's
-    counter RNG. Everything else — CPU, fp32, long sequences,
+    counter RNG. causal (ops.attention) takes the node with mask = None
+    wherever functions.attn_causal_enabled selects the hand kernels.
+    Everything else — CPU, fp32, long sequences,
     SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
     paths — is the composition of ops.linear, ops.attention and
     ops.linear_residual_layer_norm."""
     B, S, H = hidden.shape
     d = H // num_heads
+    causal = causal and S > 1  # the identity at S = 1
     # ids the node cannot take (next to a mask, wrong shape or type) go to
     # ops.attention, which raises for them
     ids_ok = segment_ids is None or (
         mask is None and segment_ids.shape == (B, S)
         and not segment_ids.is_floating_point())
     if (
-        ids_ok and hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
+        ids_ok and not (causal and mask is not None)
+        and hidden.is_cuda and hidden.dtype == torch.bfloat16 and d == 64
         and qkv_bias is not None and out_bias is not None
         and hiplib.available()
         and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
@@ -287,11 +347,14 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
         and os.environ.get("SKY_ATTN_FUSED_BWD") != "1"
     ):
         from .functions import (
-            AttentionBlockFn, attn_block_enabled, attn_long_enabled,
-            attn_seg_enabled, ln_dbias_enabled, ln_xsum_width_ok,
+            AttentionBlockFn, attn_block_enabled, attn_causal_enabled,
+            attn_long_enabled, attn_seg_enabled, ln_dbias_enabled,
+            ln_xsum_width_ok,
         )
 
-        if segment_ids is not None:
+        if causal:
+            fused = attn_causal_enabled(S)
+        elif segment_ids is not None:
             fused = attn_seg_enabled(S)
         else:
             fused = S <= 128 or attn_long_enabled(S)
@@ -301,12 +364,11 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
         ):
             ap = attn_dropout_p if (training and attn_dropout_p > 0) else 0.0
             hp = hidden_dropout_p if training else 0.0
-            return AttentionBlockFn.apply(
-                hidden, qkv_weight, qkv_bias, mask, num_heads, ap,
-                out_weight, out_bias, ln_weight, ln_bias, eps, hp, segment_ids
-            )
+            args = (hidden, qkv_weight, qkv_bias, mask, num_heads, ap,
+                    out_weight, out_bias, ln_weight, ln_bias, eps, hp, segment_ids)
+            return AttentionBlockFn.apply(*args, *((True,) if causal else ()))
     qkv = linear(hidden, qkv_weight, qkv_bias).view(B, S, 3, num_heads, d)
-    attn = attention(qkv, mask, attn_dropout_p, training, segment_ids)
+    attn = attention(qkv, mask, attn_dropout_p, training, segment_ids, causal)
     return linear_residual_layer_norm(
         attn, out_weight, out_bias, ln_weight, ln_bias, eps, hidden,
         hidden_dropout_p, training)

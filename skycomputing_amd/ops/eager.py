@@ -125,6 +125,11 @@ def segment_mask(segment_ids: torch.Tensor, check: bool = True) -> torch.Tensor:
     return same
 
 
+def causal_mask(S: int, device=None) -> torch.Tensor:
+    """Boolean [1, 1, S, S], true where key <= query (the lower triangle)."""
+    return torch.ones(S, S, dtype=torch.bool, device=device).tril_()[None, None]
+
+
 def linear_act(
     x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, act: str = "gelu"
 ) -> torch.Tensor:

@@ -364,6 +364,34 @@ def attn_seg_enabled(S: int) -> bool:
     return e == "1" if e in ("0", "1") else _ATTN_SEG_SHORT_DEFAULT
 
 
+# SKY_ATTN_CAUSAL unset: the (lo, hi] range of S at which causal attention
+# runs the triangle mode of the hand kernels by default: 2 <= S <= 2048. At
+# S = 128, 512 and 2048 (h = 16, 4096 tokens, bf16, p = 0.1) its forward +
+# backward median was below sdpa(is_causal=True)'s with non-overlapping
+# ranges in both runs: 129 / 65 against 202 / 198, 148 against 271 and 474
+# against 614 us (profiles/r16_notes.md). Above 2048 nothing was measured and
+# sdpa stays; SKY_ATTN_CAUSAL=1 opts in.
+_ATTN_CAUSAL_DEFAULT = (1, 2048)
+
+
+def attn_causal_enabled(S: int) -> bool:
+    """Whether ops.attention / ops.attention_block run the hand kernels'
+    causal (triangle) mode at this S, 2 <= S <= 4096: SKY_ATTN_CAUSAL=1 / 0
+    forces it, unset by measurement. Never under an env switch that selects
+    another S <= 128 attention path, nor above 128 under SKY_ATTN_LONG=0.
+    S = 1: never (the dense path; causal is the identity there)."""
+    if not 2 <= S <= ATTN_LONG_SMAX or any(os.environ.get(v) == "1" for v in (
+            "SKY_NO_FUSED_ATTN", "SKY_NO_FUSED_ATTN_BWD", "SKY_ATTN_FUSED_BWD")):
+        return False
+    if S > ATTN_SMAX and os.environ.get("SKY_ATTN_LONG") == "0":
+        return False
+    e = os.environ.get("SKY_ATTN_CAUSAL")
+    if e in ("0", "1"):
+        return e == "1"
+    return (_ATTN_CAUSAL_DEFAULT is not None
+            and _ATTN_CAUSAL_DEFAULT[0] < S <= _ATTN_CAUSAL_DEFAULT[1])
+
+
 def _attn_seg(segment_ids):
     """Segment ids as the kernels take them: (int32 ids,) for S <= 128, where
     the kernels find their ranges from the ids, (ids, bounds) above."""
@@ -382,11 +410,19 @@ def attn_seg_bounds(ids):
     return bounds
 
 
-def _attn_fwd(qkv, mask, scale, keep, seg=None):
+def _attn_ids(seg, n):
+    """The n pointers (ids, or ids and bounds) a causal entry point takes in
+    the segment form's place: 0s without ids."""
+    return tuple(ptr(t) for t in seg) if seg else (0,) * n
+
+
+def _attn_fwd(qkv, mask, scale, keep, seg=None, causal=False):
     """sky_attn_fwd (S <= 128) or sky_attn_long_fwd on a contiguous packed
     qkv [B, S, 3, h, 64]; draws the dropout salt when keep < 1. Returns
     (out [B, S, h, d], m, lsum, salt). seg (_attn_seg): the segment form,
-    sky_attn_long_seg_fwd on (ids, bounds) or sky_attn_seg_fwd on (ids,)."""
+    sky_attn_long_seg_fwd on (ids, bounds) or sky_attn_seg_fwd on (ids,).
+    causal: sky_attn_long_causal_fwd / sky_attn_causal_fwd, with or without
+    seg."""
     lib = hiplib.require()
     B, S, _, h, d = qkv.shape
     out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
@@ -394,7 +430,11 @@ def _attn_fwd(qkv, mask, scale, keep, seg=None):
     lsum = torch.empty_like(m)
     salt = _next_seed() if keep < 1.0 else 0
     state = rng_state()
-    if seg is not None:
+    if causal:
+        long_ = S > ATTN_SMAX
+        name = "sky_attn_long_causal_fwd" if long_ else "sky_attn_causal_fwd"
+        masks = _attn_ids(seg, 2 if long_ else 1)
+    elif seg is not None:
         name = "sky_attn_long_seg_fwd" if S > ATTN_SMAX else "sky_attn_seg_fwd"
         masks = tuple(ptr(t) for t in seg)
     else:
@@ -458,25 +498,32 @@ class FusedAttentionFn(torch.autograd.Function):
     S = 128 the block bounds are computed once and saved with them, up to
     S = 128 each wave finds its range from the ids (the segment mode of the
     keys-on-rows kernels; the env switches of the backward do not apply).
+    causal (2 <= S <= 4096, no mask, with or without segment_ids): q attends
+    k iff k <= q, and the ids equal where given: the triangle mode of the
+    same kernels, which skip the tiles and chunks past the diagonal. Nothing
+    beyond the segment mode's tensors is saved, and nothing at all for the
+    triangle itself.
     Returns [B, S, h, d].
     """
 
     @staticmethod
-    def forward(ctx, qkv, mask, scale, dropout_p, training, segment_ids=None):
+    def forward(ctx, qkv, mask, scale, dropout_p, training, segment_ids=None,
+                causal=False):
         B, S, three, h, d = qkv.shape
         assert three == 3 and d == 64 and S <= ATTN_LONG_SMAX
         qkv = qkv.contiguous()
         mask = mask.contiguous() if mask is not None else None
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
+        assert not causal or (mask is None and S >= 2)
         seg = ()
         if segment_ids is not None:
             assert mask is None and S >= 2 and segment_ids.shape == (B, S)
             seg = _attn_seg(segment_ids)
-        out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep, seg or None)
+        out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep, seg or None, causal)
         # the long backward takes its row dots from dO * O
         extra = (out,) if S > ATTN_SMAX else ()
         ctx.save_for_backward(qkv, mask, m, lsum, *extra, *seg)
-        ctx.scale, ctx.keep, ctx.salt = scale, keep, salt
+        ctx.scale, ctx.keep, ctx.salt, ctx.causal = scale, keep, salt, causal
         return out
 
     @staticmethod
@@ -494,27 +541,32 @@ class FusedAttentionFn(torch.autograd.Function):
             args = _attn_long_bwd_args(
                 qkv, dout, extra[0], mask, m, lsum, dot, dqkv, ctx.scale,
                 ctx.keep, ctx.salt)
-            if len(extra) == 3:  # (out, ids, bounds): the segment form
+            if ctx.causal:  # (out,) or (out, ids, bounds)
+                args = args[:4] + _attn_ids(extra[1:], 2) + args[5:]
+                check(lib.sky_attn_long_causal_bwd(*args), "sky_attn_long_causal_bwd")
+            elif len(extra) == 3:  # (out, ids, bounds): the segment form
                 args = args[:4] + (ptr(extra[1]), ptr(extra[2])) + args[5:]
                 check(lib.sky_attn_long_seg_bwd(*args), "sky_attn_long_seg_bwd")
             else:
                 check(lib.sky_attn_long_bwd(*args), "sky_attn_long_bwd")
-            return dqkv, None, None, None, None, None
-        if extra:
-            # (ids,): the segment mode of the keys-on-rows pair; its only
-            # scratch is the fp32 row dots, passed in pdT's place
+            return dqkv, None, None, None, None, None, None
+        if extra or ctx.causal:
+            # (ids,): the segment mode of the keys-on-rows pair (causal: its
+            # triangle mode, with or without ids); its only scratch is the
+            # fp32 row dots, passed in pdT's place
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)
             dot = torch.empty(B * h * S, dtype=torch.float32, device=dev)
+            entry = "sky_attn_causal_bwd" if ctx.causal else "sky_attn_seg_bwd"
             check(
-                lib.sky_attn_seg_bwd(
-                    _stream(), ptr(qkv), ptr(dout), ptr(extra[0]), ptr(m),
+                getattr(lib, entry)(
+                    _stream(), ptr(qkv), ptr(dout), *_attn_ids(extra, 1), ptr(m),
                     ptr(lsum), ptr(dot), 0, ptr(dqkv), B, S, h, d, ctx.scale,
                     ctx.keep, ctx.salt, rng_state().data_ptr(),
                 ),
-                "sky_attn_seg_bwd",
+                entry,
             )
-            return dqkv, None, None, None, None, None
+            return dqkv, None, None, None, None, None, None
         if os.environ.get("SKY_NO_FUSED_ATTN_BWD") != "1":
             dout = dout.contiguous()
             dqkv = torch.empty_like(qkv)
@@ -531,7 +583,7 @@ class FusedAttentionFn(torch.autograd.Function):
                     ),
                     "sky_attn_bwd_fused",
                 )
-                return dqkv, None, None, None, None, None
+                return dqkv, None, None, None, None, None, None
             # two-kernel path (bwd1s + bwd2 over transposed scratch)
             pdT, dsT = _attn_bwd_scratch(qkv)
             check(
@@ -543,7 +595,7 @@ class FusedAttentionFn(torch.autograd.Function):
                 ),
                 "sky_attn_bwd",
             )
-            return dqkv, None, None, None, None, None
+            return dqkv, None, None, None, None, None, None
         P = torch.empty(B, h, S, S, dtype=qkv.dtype, device=dev)
         Pd = torch.empty_like(P) if ctx.keep < 1.0 else P
         check(
@@ -565,7 +617,7 @@ class FusedAttentionFn(torch.autograd.Function):
             return dPd
 
         dqkv = _attn_bwd_decomposed(qkv, P, Pd, dout, ctx.scale, dP_of)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 class FlashAttentionFn(torch.autograd.Function):
@@ -1028,11 +1080,12 @@ class AttentionBlockFn(torch.autograd.Function):
     segment_ids (packed sequences, S >= 2) in place of mask: integer [B, S]
     as in FusedAttentionFn, whose segment forward this runs; the backward
     takes the segment forms of the dbias entry points (the bounds table of
-    S > 128 is computed once in forward and saved)."""
+    S > 128 is computed once in forward and saved). causal (S >= 2, no mask,
+    with or without segment_ids): the triangle mode, as FusedAttentionFn."""
 
     @staticmethod
     def forward(ctx, hidden, wqkv, bqkv, mask, num_heads, attn_p, wo, bo,
-                ln_w, ln_b, eps, hidden_p, segment_ids=None):
+                ln_w, ln_b, eps, hidden_p, segment_ids=None, causal=False):
         B, S, H = hidden.shape
         d = H // num_heads
         assert d == 64 and S <= ATTN_LONG_SMAX and hidden.dtype == torch.bfloat16
@@ -1042,11 +1095,13 @@ class AttentionBlockFn(torch.autograd.Function):
         mask = mask.contiguous() if mask is not None else None
         scale = 1.0 / math.sqrt(d)
         akeep = 1.0 - attn_p
+        assert not causal or (mask is None and S >= 2)
         seg = ()
         if segment_ids is not None:
             assert mask is None and S >= 2 and segment_ids.shape == (B, S)
             seg = _attn_seg(segment_ids)
-        ctxl, m, lsum, asalt = _attn_fwd(qkv, mask, scale, akeep, seg or None)
+        ctxl, m, lsum, asalt = _attn_fwd(qkv, mask, scale, akeep, seg or None,
+                                         causal)
         c2 = ctxl.view(-1, H)
         h = _linear_fwd(c2, wo, bo).view(B, S, H)
         keep = 1.0 - hidden_p
@@ -1054,7 +1109,7 @@ class AttentionBlockFn(torch.autograd.Function):
         ctx.save_for_backward(x2, wqkv, qkv, mask, m, lsum, c2, wo, h, ln_w,
                               mean, rstd, *seg)
         ctx.scale, ctx.akeep, ctx.asalt = scale, akeep, asalt
-        ctx.keep, ctx.salt = keep, salt
+        ctx.keep, ctx.salt, ctx.causal = keep, salt, causal
         return y
 
     @staticmethod
@@ -1077,7 +1132,7 @@ class AttentionBlockFn(torch.autograd.Function):
         dbqkv = torch.empty(3 * H, dtype=wqkv.dtype, device=qkv.device)
         # the S <= 128 scratch first, then the slabs: the allocation order
         # this node has always had
-        if S > ATTN_SMAX or seg:
+        if S > ATTN_SMAX or seg or ctx.causal:
             scratch = (torch.empty(B * nh * S, dtype=torch.float32, device=qkv.device),)
         else:
             scratch = _attn_bwd_scratch(qkv)
@@ -1091,13 +1146,17 @@ class AttentionBlockFn(torch.autograd.Function):
             entry = "sky_attn_long_bwd_dbias"
             args = _attn_long_bwd_args(qkv, dctx, c2, mask, m, lsum, scratch[0],
                                        dqkv, ctx.scale, ctx.akeep, ctx.asalt)
-            if seg:  # (ids, bounds) in the mask's place
+            if ctx.causal:  # (ids, bounds) or (0, 0) in the mask's place
+                entry = "sky_attn_long_causal_bwd_dbias"
+                args = args[:4] + _attn_ids(seg, 2) + args[5:]
+            elif seg:  # (ids, bounds) in the mask's place
                 entry = "sky_attn_long_seg_bwd_dbias"
                 args = args[:4] + (ptr(seg[0]), ptr(seg[1])) + args[5:]
-        elif seg:
-            # (ids,) in the mask's place; the row dots are the only scratch
-            entry = "sky_attn_seg_bwd_dbias"
-            args = (_stream(), ptr(qkv), ptr(dctx), ptr(seg[0]), ptr(m),
+        elif seg or ctx.causal:
+            # (ids,) in the mask's place (causal: ids or 0); the row dots are
+            # the only scratch
+            entry = "sky_attn_causal_bwd_dbias" if ctx.causal else "sky_attn_seg_bwd_dbias"
+            args = (_stream(), ptr(qkv), ptr(dctx), *_attn_ids(seg, 1), ptr(m),
                     ptr(lsum), ptr(scratch[0]), 0, ptr(dqkv), B, S, nh, d,
                     ctx.scale, ctx.akeep, ctx.asalt, rng_state().data_ptr())
         else:
@@ -1128,7 +1187,7 @@ class AttentionBlockFn(torch.autograd.Function):
         if dbo.dtype != wo.dtype:
             dbo = dbo.to(wo.dtype)
         return (dres.view(B, S, H), dwqkv, dbqkv, None, None, None, dwo, dbo,
-                d_ln_w, d_ln_b, None, None, None)
+                d_ln_w, d_ln_b, None, None, None, None)
 
 
 def _linear_gelu_fwd(x2, weight, bias):

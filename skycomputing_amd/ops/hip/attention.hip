@@ -276,7 +276,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(
 #define KR_MASK_OFF KR_AUX_OFF
 #define KR_LDS_BYTES (KR_AUX_OFF + 512)
 
-template <bool HAS_MASK, int QPW, bool SEG = false>
+// CAUSAL (QPW = 1, no additive mask, with or without SEG): query q sees key k
+// iff k <= q. The mask is a position compare (att_tri_mask4, with SEG the id
+// compare in the same select) and a wave's key range ends with its own tile
+// (att_tri_range), so the tiles above the diagonal are skipped like foreign
+// segments' tiles. Without ids nothing is put in the mask's LDS slot.
+template <bool HAS_MASK, int QPW, bool SEG = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
     ushort_t* __restrict__ out, float* __restrict__ m_io,
@@ -310,8 +315,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
   att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KR_K_OFF, tid);
   att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KR_V_OFF, tid);
   static_assert(!SEG || (QPW == 1 && !HAS_MASK), "segment mode: QPW = 1, no mask");
+  static_assert(!CAUSAL || (QPW == 1 && !HAS_MASK), "causal mode: QPW = 1, no mask");
   if constexpr (SEG) att_seg_ids_lds((int*)mk, (const int*)mask, b, S, tid);
-  else att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  else if constexpr (!CAUSAL) att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -334,18 +340,23 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_krows_kernel(
       int lo, hi;
       att_seg_wave_range(lo, hi, sk, __builtin_amdgcn_readlane(qid, 0),
                          __builtin_amdgcn_readlane(qid, 15), S, l);
-      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+      if constexpr (CAUSAL) att_tri_range(t0, t1, p0, p1, lo, hi, qtok_base, true);
+      else t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    } else if constexpr (CAUSAL) {
+      att_tri_range(t0, t1, p0, p1, 0, S, qtok_base, true);
     }
     f32x4 sacc[8];
     att_zero(sacc);
-    if constexpr (SEG) att_score_tile_t_range(sacc, bq, lds, KR_K_OFF, t0, t1, lm, lg);
+    if constexpr (SEG || CAUSAL)
+      att_score_tile_t_range(sacc, bq, lds, KR_K_OFF, t0, t1, lm, lg);
     else att_score_tile_t(sacc, bq, lds, KR_K_OFF, NT, lm, lg);
     float mx = -3.0e38f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
       if (mt < t0 || mt >= t1) continue;
       f32x4 mv;
-      if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
+      if constexpr (CAUSAL) mv = att_tri_mask4<SEG>((const int*)mk, mt, lg, qid, qc, S);
+      else if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
       else mv = att_mask_keys4(mk, mt, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -531,6 +542,29 @@ SKY_EXPORT int sky_attn_seg_fwd(uint64_t stream, uint64_t qkv, uint64_t ids,
                      (const ushort_t*)ids, (ushort_t*)out, (float*)m,
                      (float*)lsum, (int)B, (int)S, (int)h, scale, keep, salt,
                      (const unsigned long long*)state);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// The causal form (q attends k iff k <= q), arguments as sky_attn_seg_fwd.
+// ids may be 0: no packing, the whole row is one triangle; otherwise both
+// conditions hold. 2 <= S <= 128, d = 64, always the keys-on-rows kernel.
+SKY_EXPORT int sky_attn_causal_fwd(uint64_t stream, uint64_t qkv, uint64_t ids,
+                                   uint64_t out, uint64_t m, uint64_t lsum,
+                                   int64_t B, int64_t S, int64_t h, int64_t d,
+                                   float scale, float keep, uint64_t salt,
+                                   uint64_t state) {
+  if (d != ATT_D || S < 2 || S > ATT_SMAX) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+#define ATTC(SEG)                                                             \
+  hipLaunchKernelGGL((attn_fwd_krows_kernel<false, 1, SEG, true>), grid,      \
+                     dim3(256), KR_LDS_BYTES, (hipStream_t)stream,            \
+                     (const ushort_t*)qkv, (const ushort_t*)ids,              \
+                     (ushort_t*)out, (float*)m, (float*)lsum, (int)B, (int)S, \
+                     (int)h, scale, keep, salt,                               \
+                     (const unsigned long long*)state)
+  if (ids) ATTC(true); else ATTC(false);
+#undef ATTC
   LAUNCH_CHECK();
   return 0;
 }

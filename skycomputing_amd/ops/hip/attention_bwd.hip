@@ -583,7 +583,11 @@ SKY_EXPORT int sky_attn_bwd_fused(uint64_t stream, uint64_t qkv,
 #define KRB_SUM_OFF (KR_AUX_OFF + 512)
 #define KRB_DQ_LDS (KR_AUX_OFF + 512 + 1024)
 
-template <bool HAS_MASK, bool DBIAS, bool SEG = false>
+// CAUSAL in both kernels, with or without SEG (attn_fwd_krows_kernel): a pair
+// with key > query gets the same -3e38 from a position compare, and the wave's
+// range is cut to the triangle (att_tri_range): the dQ kernel's keys end with
+// the wave's own tile, the dK/dV kernel's queries begin with it.
+template <bool HAS_MASK, bool DBIAS, bool SEG = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
@@ -624,8 +628,9 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
   att_glds_rows(kbase, ts, 0, NP * 32, true, S, lds, KRB_K_OFF, tid);
   att_glds_rows(vbase, ts, 0, NP * 32, true, S, lds, KRB_V_OFF, tid);
   static_assert(!SEG || !HAS_MASK, "segment mode takes ids in the mask's place");
+  static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
   if constexpr (SEG) att_seg_ids_lds((int*)mk, (const int*)mask, b, S, tid);
-  else att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
+  else if constexpr (!CAUSAL) att_mask_keys_lds(mk, HAS_MASK, mask, b, S, tid);
   bf16x8 bq[2], bdo[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
@@ -647,12 +652,15 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
       int lo, hi;
       att_seg_wave_range(lo, hi, sk, __builtin_amdgcn_readlane(qid, 0),
                          __builtin_amdgcn_readlane(qid, 15), S, l);
-      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+      if constexpr (CAUSAL) att_tri_range(t0, t1, p0, p1, lo, hi, qtok_base, true);
+      else t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    } else if constexpr (CAUSAL) {
+      att_tri_range(t0, t1, p0, p1, 0, S, qtok_base, true);
     }
     f32x4 sacc[8], dacc[8];
     att_zero(sacc);
     att_zero(dacc);
-    if constexpr (SEG) {
+    if constexpr (SEG || CAUSAL) {
       att_score_tile_t_range(sacc, bq, lds, KRB_K_OFF, t0, t1, lm, lg);
       att_score_tile_t_range(dacc, bdo, lds, KRB_V_OFF, t0, t1, lm, lg);
     } else {
@@ -667,7 +675,8 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
     for (int mt = 0; mt < 8; ++mt) {
       if (mt < t0 || mt >= t1) continue;
       f32x4 mv;
-      if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
+      if constexpr (CAUSAL) mv = att_tri_mask4<SEG>((const int*)mk, mt, lg, qid, qc, S);
+      else if constexpr (SEG) mv = att_seg_mask4((const int*)mk, mt, lg, qid, S);
       else mv = att_mask_keys4(mk, mt, lg);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -743,7 +752,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_krows_kernel(
 #define KRB_QID_OFF KRB_DKV_LDS
 #define KRB_DKV_SEG_LDS (KRB_DKV_LDS + 512)
 
-template <bool HAS_MASK, bool DBIAS, bool SEG = false>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
@@ -820,7 +829,10 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
       int lo, hi;
       att_seg_wave_range(lo, hi, sq, __builtin_amdgcn_readlane(kid, 0),
                          __builtin_amdgcn_readlane(kid, 15), S, l);
-      t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+      if constexpr (CAUSAL) att_tri_range(t0, t1, p0, p1, lo, hi, ktok_base, false);
+      else t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+    } else if constexpr (CAUSAL) {
+      att_tri_range(t0, t1, p0, p1, 0, S, ktok_base, false);
     }
     f32x4 kacc[4], vacc[4];
     att_zero(kacc);
@@ -857,7 +869,9 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = qt * 16 + lg * 4 + r;
-          const float mvr = (SEG && qid4[r] != kid) ? -3.0e38f : mv;
+          // the lane's token is the key here: the triangle compare turns round
+          const float mvr = ((SEG && qid4[r] != kid) || (CAUSAL && qq < key))
+                                ? -3.0e38f : mv;
           const float p = att_prob(s4[r], scale, mvr, m4[r], il4[r],
                                    qq < S && key < S);
           const bool kbit = (kbits >> (8 * r + w)) & 1u;
@@ -909,7 +923,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_krows_kernel(
 // the default pair: dQ + dot, then dK/dV. dot (fp32 [B*h*S]) lives at the
 // head of the pdT scratch the entry points receive (2*S*S bytes per (b,h)
 // cover 4*S for S >= 2); nothing else of pdT / dsT is touched.
-template <bool DBIAS, bool SEG = false>
+template <bool DBIAS, bool SEG = false, bool CAUSAL = false>
 static void launch_attn_bwd_krows(hipStream_t s, uint64_t qkv, uint64_t dout,
                                   uint64_t mask, uint64_t m, uint64_t lsum,
                                   uint64_t pdT, uint64_t dqkv, int64_t B,
@@ -917,15 +931,16 @@ static void launch_attn_bwd_krows(hipStream_t s, uint64_t qkv, uint64_t dout,
                                   float keep, uint64_t salt, uint64_t state,
                                   float* dbscr) {
   dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
-  if constexpr (SEG) {  // mask: the int32 segment ids
-    hipLaunchKernelGGL((attn_bwd_dq_krows_kernel<false, DBIAS, true>), grid,
+  if constexpr (SEG || CAUSAL) {  // mask: the int32 segment ids (SEG) or unused
+    hipLaunchKernelGGL((attn_bwd_dq_krows_kernel<false, DBIAS, SEG, CAUSAL>), grid,
                        dim3(256), KRB_DQ_LDS, s, (const ushort_t*)qkv,
                        (const ushort_t*)dout, (const ushort_t*)mask,
                        (const float*)m, (const float*)lsum, (float*)pdT,
                        (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep,
                        salt, (const unsigned long long*)state, dbscr);
-    hipLaunchKernelGGL((attn_bwd_dkv_krows_kernel<false, DBIAS, true>), grid,
-                       dim3(256), KRB_DKV_SEG_LDS, s, (const ushort_t*)qkv,
+    hipLaunchKernelGGL((attn_bwd_dkv_krows_kernel<false, DBIAS, SEG, CAUSAL>), grid,
+                       dim3(256), SEG ? KRB_DKV_SEG_LDS : KRB_DKV_LDS, s,
+                       (const ushort_t*)qkv,
                        (const ushort_t*)dout, (const ushort_t*)mask,
                        (const float*)m, (const float*)lsum, (const float*)pdT,
                        (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep,
@@ -1006,11 +1021,20 @@ static int attn_bwd_dbias_impl(uint64_t stream, uint64_t qkv, uint64_t dout,
                                float scale, float keep, uint64_t salt,
                                uint64_t state, uint64_t scratch,
                                uint64_t dbias, int dbias_dt,
-                               SkyFinishJob* job, bool seg = false) {
+                               SkyFinishJob* job, bool seg = false,
+                               bool causal = false) {
   if (d != ATT_D || S > ATT_SMAX || scratch == 0 || dbias == 0)
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  if (seg)  // mask: the segment ids; the caller has checked the shape
+  if (causal && seg)  // causal: seg says whether mask holds ids
+    launch_attn_bwd_krows<true, true, true>(s, qkv, dout, mask, m, lsum, pdT,
+                                            dqkv, B, S, h, scale, keep, salt,
+                                            state, (float*)scratch);
+  else if (causal)
+    launch_attn_bwd_krows<true, false, true>(s, qkv, dout, 0, m, lsum, pdT,
+                                             dqkv, B, S, h, scale, keep, salt,
+                                             state, (float*)scratch);
+  else if (seg)  // mask: the segment ids; the caller has checked the shape
     launch_attn_bwd_krows<true, true>(s, qkv, dout, mask, m, lsum, pdT, dqkv, B,
                                       S, h, scale, keep, salt, state,
                                       (float*)scratch);
@@ -1104,4 +1128,55 @@ SKY_EXPORT int sky_attn_seg_bwd_dbias_parts(
   return attn_bwd_dbias_impl(stream, qkv, dout, ids, m, lsum, pdT, dsT, dqkv,
                              B, S, h, d, scale, keep, salt, state, scratch,
                              dbias, dbias_dt, (SkyFinishJob*)job, true);
+}
+
+// The causal forms of the three entry points above, after sky_attn_causal_fwd:
+// arguments as the segment forms, but ids may be 0 (no packing). 2 <= S <= 128
+// and d = 64; only the fp32 row dots at the head of pdT are written.
+static bool attn_causal_shape_ok(int64_t S, int64_t d, uint64_t pdT) {
+  return d == ATT_D && S >= 2 && S <= ATT_SMAX && pdT != 0;
+}
+
+SKY_EXPORT int sky_attn_causal_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
+                                   uint64_t ids, uint64_t m, uint64_t lsum,
+                                   uint64_t pdT, uint64_t dsT, uint64_t dqkv,
+                                   int64_t B, int64_t S, int64_t h, int64_t d,
+                                   float scale, float keep, uint64_t salt,
+                                   uint64_t state) {
+  if (!attn_causal_shape_ok(S, d, pdT)) return (int)hipErrorInvalidValue;
+  if (ids)
+    launch_attn_bwd_krows<false, true, true>((hipStream_t)stream, qkv, dout, ids,
+                                             m, lsum, pdT, dqkv, B, S, h, scale,
+                                             keep, salt, state, nullptr);
+  else
+    launch_attn_bwd_krows<false, false, true>((hipStream_t)stream, qkv, dout, 0,
+                                              m, lsum, pdT, dqkv, B, S, h, scale,
+                                              keep, salt, state, nullptr);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_causal_bwd_dbias(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t ids, uint64_t m,
+    uint64_t lsum, uint64_t pdT, uint64_t dsT, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt) {
+  if (!attn_causal_shape_ok(S, d, pdT)) return (int)hipErrorInvalidValue;
+  return attn_bwd_dbias_impl(stream, qkv, dout, ids, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, nullptr, ids != 0, true);
+}
+
+SKY_EXPORT int sky_attn_causal_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t ids, uint64_t m,
+    uint64_t lsum, uint64_t pdT, uint64_t dsT, uint64_t dqkv, int64_t B,
+    int64_t S, int64_t h, int64_t d, float scale, float keep, uint64_t salt,
+    uint64_t state, uint64_t scratch, uint64_t dbias, int dbias_dt,
+    uint64_t job) {
+  if (job == 0 || !attn_causal_shape_ok(S, d, pdT))
+    return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_bwd_dbias_impl(stream, qkv, dout, ids, m, lsum, pdT, dsT, dqkv,
+                             B, S, h, d, scale, keep, salt, state, scratch,
+                             dbias, dbias_dt, (SkyFinishJob*)job, ids != 0, true);
 }

@@ -128,8 +128,30 @@ DEV void atl_seg_chunks(int& c0, int& c1, const int* __restrict__ bounds,
 #define ATL_MASK_OFF KR_AUX_OFF
 #define ATL_FWD_LDS (KR_AUX_OFF + 512)
 
+// The chunk range of 64-token block blk under the triangle, cut from [c0, c1):
+// a query block ends with the chunk that holds its last query (the chunks past
+// its diagonal are never staged), a key block begins with the chunk that holds
+// its first key. Block-uniform: the chunk loops hold barriers.
+DEV int atl_tri_last_chunk(int c1, int blk) {
+  const int d = (blk * 64 + 63) / 128 + 1;
+  return c1 < d ? c1 : d;
+}
+DEV int atl_tri_first_chunk(int c0, int blk) {
+  const int d = blk * 64 / 128;
+  return c0 > d ? c0 : d;
+}
+// the tiles of a chunk a wave visits: up to the one that holds its first
+// query, rel = 16-aligned query base minus the chunk's first key (>= 0)
+DEV int atl_tri_tiles(int nt, int rel) {
+  const int d = (rel >> 4) + 1;
+  return nt < d ? nt : d;
+}
+
 // SEG: mask points at the int32 segment ids [B][S], bounds at the table.
-template <bool HAS_MASK, bool SEG = false>
+// CAUSAL (no additive mask, with or without SEG): q sees k iff k <= q. The
+// block stops at its diagonal chunk, and inside it a wave stops at its own
+// diagonal tile; without ids neither mask nor bounds is read.
+template <bool HAS_MASK, bool SEG = false, bool CAUSAL = false>
 ATL_KERNEL void attn_fwd_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
     ushort_t* __restrict__ out, float* __restrict__ m_io,
@@ -172,6 +194,8 @@ ATL_KERNEL void attn_fwd_long_kernel(
     atl_seg_chunks(kc0, kc1, bounds, b, QB, qb, NCH);
     qid = ids[(size_t)b * S + qc];
   }
+  static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
+  if constexpr (CAUSAL) kc1 = atl_tri_last_chunk(kc1, qb);
 
   // Chunk 0 always holds key 0 and additive masks are finite (-10000), so m
   // is a real score after chunk 0. Before it, m = -3e38 gives alpha =
@@ -187,6 +211,14 @@ ATL_KERNEL void attn_fwd_long_kernel(
   // lane's first visible chunk as exact zeros, and no inf - inf can form
   // because m is never infinite. With a visible key m_new is a real score
   // and the clamp does nothing.
+  // CAUSAL without ids: the walk starts at chunk 0, whose key 0 every query
+  // sees, so m is a real score after it as in the dense case; every later
+  // chunk the block visits starts at or before the block's first query, so
+  // no lane ever meets a chunk without a visible key, and the keys above the
+  // diagonal are -3e38 against a real m: exact zeros. With ids the SEG
+  // argument applies unchanged: the triangle only removes keys, the lane's
+  // own key (the diagonal) is in its run and in the walk, and a chunk left
+  // with no visible key is the case the clamp covers.
   float m = -3.0e38f, lsum = 0.f;
   f32x4 oacc[4];
   att_zero(oacc);
@@ -203,22 +235,29 @@ ATL_KERNEL void attn_fwd_long_kernel(
     att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
     att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
     if constexpr (SEG) atl_seg_ids_lds_at((int*)mk, ids, b, S, k0, tid);
-    else att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    else if constexpr (!CAUSAL) att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (!active) continue;
     int lmc, lgc;
     atl_chunk_lanes(lmc, lgc, lm, lg);
+    // CAUSAL: the wave's tiles end with its diagonal tile (wave-uniform; NT
+    // again in every chunk before the diagonal one); a skipped tile keeps
+    // att_zero's zeros through to the PV pair that holds it
+    const int NTw = CAUSAL ? atl_tri_tiles(NT, qtok_base - k0) : NT;
+    const int NPw = CAUSAL ? (NTw + 1) >> 1 : NP;
 
     f32x4 sacc[8];
     att_zero(sacc);
-    att_score_tile_t(sacc, bq, lds, ATL_K_OFF, NT, lmc, lgc);
+    att_score_tile_t(sacc, bq, lds, ATL_K_OFF, NTw, lmc, lgc);
     float mx = -3.0e38f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
+      if (mt >= NTw) continue;
       f32x4 mv;
-      if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
+      if constexpr (CAUSAL)
+        mv = att_tri_mask4<SEG>((const int*)mk, mt, lgc, qid, q - k0, nk);
+      else if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
       else mv = att_mask_keys4(mk, mt, lgc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -240,7 +279,7 @@ ATL_KERNEL void attn_fwd_long_kernel(
     float sm = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
-      if (mt >= NT) continue;
+      if (mt >= NTw) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = __expf(sacc[mt][r] - m_exp);
@@ -258,7 +297,7 @@ ATL_KERNEL void attn_fwd_long_kernel(
     // O^T += V^T Pd^T: B = the score registers, A = V^T by tr16
 #pragma unroll
     for (int kp = 0; kp < 4; ++kp) {
-      if (kp >= NP) continue;
+      if (kp >= NPw) continue;
       const bf16x8 bp = att_pack_dpair(sacc[2 * kp], sacc[2 * kp + 1]);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
@@ -289,7 +328,7 @@ ATL_KERNEL void attn_fwd_long_kernel(
 #define ATL_SUM_OFF (KR_AUX_OFF + 512)
 #define ATL_DQ_LDS (KR_AUX_OFF + 512 + 1024)
 
-template <bool HAS_MASK, bool DBIAS, bool SEG = false>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false, bool CAUSAL = false>
 ATL_KERNEL void attn_bwd_dq_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ out, const ushort_t* __restrict__ mask,
@@ -357,6 +396,8 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
     atl_seg_chunks(kc0, kc1, bounds, b, QB, qb, NCH);
     qid = ids[(size_t)b * S + qc];
   }
+  static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
+  if constexpr (CAUSAL) kc1 = atl_tri_last_chunk(kc1, qb);
 
   f32x4 qacc[4];
   att_zero(qacc);
@@ -370,27 +411,32 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
     att_glds_rows(kbase, ts, k0, NP * 32, true, S, lds, ATL_K_OFF, tid);
     att_glds_rows(vbase, ts, k0, NP * 32, true, S, lds, ATL_V_OFF, tid);
     if constexpr (SEG) atl_seg_ids_lds_at((int*)mk, ids, b, S, k0, tid);
-    else att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
+    else if constexpr (!CAUSAL) att_mask_keys_lds_at(mk, HAS_MASK, mask, b, S, k0, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (!active) continue;
     int lmc, lgc;
     atl_chunk_lanes(lmc, lgc, lm, lg);
+    // CAUSAL: tiles and pairs up to the wave's diagonal tile, as the forward
+    const int NTw = CAUSAL ? atl_tri_tiles(NT, qtok_base - k0) : NT;
+    const int NPw = CAUSAL ? (NTw + 1) >> 1 : NP;
 
     uint64_t z[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     if (keep < 1.f) atl_drop_hash_chunk(z, seed, bh, S, q, lg, kc);
 #pragma unroll
     for (int kp = 0; kp < 4; ++kp) {
-      if (kp >= NP) continue;
+      if (kp >= NPw) continue;
       f32x4 s2[2], d2[2];
-      atl_score_pair_t(s2, bq, lds, ATL_K_OFF, kp, NT, lmc, lgc);   // K Q^T
-      atl_score_pair_t(d2, bdo, lds, ATL_V_OFF, kp, NT, lmc, lgc);  // V dO^T
+      atl_score_pair_t(s2, bq, lds, ATL_K_OFF, kp, NTw, lmc, lgc);   // K Q^T
+      atl_score_pair_t(d2, bdo, lds, ATL_V_OFF, kp, NTw, lmc, lgc);  // V dO^T
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int mt = 2 * kp + t;
-        if (mt >= NT) continue;  // s2[t] stays zero: a null dS tile
+        if (mt >= NTw) continue;  // s2[t] stays zero: a null dS tile
         f32x4 mv;
-        if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
+        if constexpr (CAUSAL)
+          mv = att_tri_mask4<SEG>((const int*)mk, mt, lgc, qid, q - k0, nk);
+        else if constexpr (SEG) mv = atl_seg_mask4((const int*)mk, mt, lgc, qid, nk);
         else mv = att_mask_keys4(mk, mt, lgc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -448,7 +494,7 @@ ATL_KERNEL void attn_bwd_dq_long_kernel(
 #define ATL_QID_OFF ATL_DKV_LDS
 #define ATL_DKV_SEG_LDS (ATL_DKV_LDS + 512)
 
-template <bool HAS_MASK, bool DBIAS, bool SEG = false>
+template <bool HAS_MASK, bool DBIAS, bool SEG = false, bool CAUSAL = false>
 ATL_KERNEL void attn_bwd_dkv_long_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
@@ -504,6 +550,9 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
     atl_seg_chunks(qc0, qc1, bounds, b, QB, kb, NCH);
     kid = ids[(size_t)b * S + kc];
   }
+  static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
+  // CAUSAL: the key block's queries begin in the chunk that holds its first key
+  if constexpr (CAUSAL) qc0 = atl_tri_first_chunk(qc0, kb);
 
   f32x4 kacc[4], vacc[4];
   att_zero(kacc);
@@ -533,10 +582,14 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
     if (!active) continue;
     int lmc, lgc;
     atl_chunk_lanes(lmc, lgc, lm, lg);
+    // CAUSAL: in the diagonal chunk the wave starts at its own tile (0 in
+    // every later chunk); wave-uniform, no barrier below
+    const int tw0 = CAUSAL && ktok_base > q0 ? (ktok_base - q0) >> 4 : 0;
 
 #pragma unroll
     for (int qp = 0; qp < 4; ++qp) {
       if (qp >= NP) continue;
+      if constexpr (CAUSAL) if (qp < tw0 >> 1) continue;
       f32x4 pd[2], ds[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -544,6 +597,7 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
         pd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         ds[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (qt >= NT) continue;
+        if constexpr (CAUSAL) if (qt < tw0) continue;
         const int qrow = qt * 16 + lmc;  // < NP*32: a staged (clamped) row
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -566,7 +620,9 @@ ATL_KERNEL void attn_bwd_dkv_long_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = q0 + qt * 16 + lg * 4 + r;
-          const float mvr = (SEG && qid4[r] != kid) ? -3.0e38f : mv;
+          // the lane's token is the key here: the triangle compare turns round
+          const float mvr = ((SEG && qid4[r] != kid) || (CAUSAL && qq < key))
+                                ? -3.0e38f : mv;
           const float p = att_prob(s4[r], scale, mvr, m4[r], il4[r],
                                    qq < S && key < S);
           const bool kbit = (kbits >> (8 * r + w)) & 1u;
@@ -805,8 +861,9 @@ SKY_EXPORT int sky_attn_long_seg_fwd(uint64_t stream, uint64_t qkv,
   return 0;
 }
 
-// the segment pair: dQ + dot, then dK/dV; DBIAS also fills the slabs
-template <bool DBIAS>
+// the segment pair: dQ + dot, then dK/dV; DBIAS also fills the slabs.
+// CAUSAL: the triangle pair, with ids and bounds (SEG) or with neither.
+template <bool DBIAS, bool SEG = true, bool CAUSAL = false>
 static void launch_attn_long_seg_bwd(hipStream_t s, uint64_t qkv, uint64_t dout,
                                      uint64_t out, uint64_t ids, uint64_t bounds,
                                      uint64_t m, uint64_t lsum, uint64_t dot,
@@ -815,15 +872,16 @@ static void launch_attn_long_seg_bwd(hipStream_t s, uint64_t qkv, uint64_t dout,
                                      uint64_t salt, uint64_t state,
                                      float* dbscr) {
   dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
-  hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, DBIAS, true>), grid,
+  hipLaunchKernelGGL((attn_bwd_dq_long_kernel<false, DBIAS, SEG, CAUSAL>), grid,
                      dim3(256), ATL_DQ_LDS, s, (const ushort_t*)qkv,
                      (const ushort_t*)dout, (const ushort_t*)out,
                      (const ushort_t*)ids, (const float*)m, (const float*)lsum,
                      (float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
                      keep, salt, (const unsigned long long*)state, dbscr,
                      (const int*)bounds);
-  hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, DBIAS, true>), grid,
-                     dim3(256), ATL_DKV_SEG_LDS, s, (const ushort_t*)qkv,
+  hipLaunchKernelGGL((attn_bwd_dkv_long_kernel<false, DBIAS, SEG, CAUSAL>), grid,
+                     dim3(256), SEG ? ATL_DKV_SEG_LDS : ATL_DKV_LDS, s,
+                     (const ushort_t*)qkv,
                      (const ushort_t*)dout, (const ushort_t*)ids,
                      (const float*)m, (const float*)lsum, (const float*)dot,
                      (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale, keep, salt,
@@ -854,14 +912,25 @@ static int attn_long_seg_bwd_dbias_impl(
     uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
     int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
     uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
-    int dbias_dt, SkyFinishJob* job) {
-  if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || ids == 0 || bounds == 0 ||
-      scratch == 0 || dbias == 0)
+    int dbias_dt, SkyFinishJob* job, bool causal = false) {
+  // causal: ids and bounds both set or both 0
+  const bool seg = ids != 0 && bounds != 0;
+  if (!atl_shape_ok(S, d) || out == 0 || dot == 0 || scratch == 0 ||
+      dbias == 0 || (causal ? (ids != 0) != (bounds != 0) : !seg))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  launch_attn_long_seg_bwd<true>(s, qkv, dout, out, ids, bounds, m, lsum, dot,
-                                 dqkv, B, S, h, scale, keep, salt, state,
-                                 (float*)scratch);
+  if (!causal)
+    launch_attn_long_seg_bwd<true>(s, qkv, dout, out, ids, bounds, m, lsum, dot,
+                                   dqkv, B, S, h, scale, keep, salt, state,
+                                   (float*)scratch);
+  else if (seg)
+    launch_attn_long_seg_bwd<true, true, true>(s, qkv, dout, out, ids, bounds, m,
+                                               lsum, dot, dqkv, B, S, h, scale,
+                                               keep, salt, state, (float*)scratch);
+  else
+    launch_attn_long_seg_bwd<true, false, true>(s, qkv, dout, out, 0, 0, m, lsum,
+                                                dot, dqkv, B, S, h, scale, keep,
+                                                salt, state, (float*)scratch);
   const int64_t cols = 3 * h * ATT_D, nslabs = B * ((S + 63) / 64);
   if (job)
     sky_finish_job_set(job, scratch, dbias, 0, 0, nslabs, cols, 1, dbias_dt);
@@ -896,4 +965,81 @@ SKY_EXPORT int sky_attn_long_seg_bwd_dbias_parts(
                                       lsum, dot, dqkv, B, S, h, d, scale, keep,
                                       salt, state, scratch, dbias, dbias_dt,
                                       (SkyFinishJob*)job);
+}
+
+// ---------------------------------------------------------------------------
+// The causal forms (q attends k iff k <= q): arguments as the segment forms
+// above, but ids and bounds may both be 0 (no packing), which selects the
+// SEG = false instantiations; only one of the two set is an error.
+static bool atl_causal_ok(int64_t S, int64_t d, uint64_t ids, uint64_t bounds) {
+  return atl_shape_ok(S, d) && (ids != 0) == (bounds != 0);
+}
+
+SKY_EXPORT int sky_attn_long_causal_fwd(uint64_t stream, uint64_t qkv,
+                                        uint64_t ids, uint64_t bounds,
+                                        uint64_t out, uint64_t m, uint64_t lsum,
+                                        int64_t B, int64_t S, int64_t h,
+                                        int64_t d, float scale, float keep,
+                                        uint64_t salt, uint64_t state) {
+  if (!atl_causal_ok(S, d, ids, bounds)) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)(B * h * ((S + 63) / 64)));
+#define ATLC(SEG)                                                             \
+  hipLaunchKernelGGL((attn_fwd_long_kernel<false, SEG, true>), grid,          \
+                     dim3(256), ATL_FWD_LDS, (hipStream_t)stream,             \
+                     (const ushort_t*)qkv, (const ushort_t*)ids,              \
+                     (ushort_t*)out, (float*)m, (float*)lsum, (int)B, (int)S, \
+                     (int)h, scale, keep, salt,                               \
+                     (const unsigned long long*)state, (const int*)bounds)
+  if (ids) ATLC(true); else ATLC(false);
+#undef ATLC
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_long_causal_bwd(uint64_t stream, uint64_t qkv,
+                                        uint64_t dout, uint64_t out,
+                                        uint64_t ids, uint64_t bounds,
+                                        uint64_t m, uint64_t lsum, uint64_t dot,
+                                        uint64_t dqkv, int64_t B, int64_t S,
+                                        int64_t h, int64_t d, float scale,
+                                        float keep, uint64_t salt,
+                                        uint64_t state) {
+  if (!atl_causal_ok(S, d, ids, bounds) || out == 0 || dot == 0)
+    return (int)hipErrorInvalidValue;
+  if (ids)
+    launch_attn_long_seg_bwd<false, true, true>(
+        (hipStream_t)stream, qkv, dout, out, ids, bounds, m, lsum, dot, dqkv, B,
+        S, h, scale, keep, salt, state, nullptr);
+  else
+    launch_attn_long_seg_bwd<false, false, true>(
+        (hipStream_t)stream, qkv, dout, out, 0, 0, m, lsum, dot, dqkv, B, S, h,
+        scale, keep, salt, state, nullptr);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+SKY_EXPORT int sky_attn_long_causal_bwd_dbias(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t ids,
+    uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
+    int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
+    uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
+    int dbias_dt) {
+  return attn_long_seg_bwd_dbias_impl(stream, qkv, dout, out, ids, bounds, m,
+                                      lsum, dot, dqkv, B, S, h, d, scale, keep,
+                                      salt, state, scratch, dbias, dbias_dt,
+                                      nullptr, true);
+}
+
+SKY_EXPORT int sky_attn_long_causal_bwd_dbias_parts(
+    uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out, uint64_t ids,
+    uint64_t bounds, uint64_t m, uint64_t lsum, uint64_t dot, uint64_t dqkv,
+    int64_t B, int64_t S, int64_t h, int64_t d, float scale, float keep,
+    uint64_t salt, uint64_t state, uint64_t scratch, uint64_t dbias,
+    int dbias_dt, uint64_t job) {
+  if (job == 0) return (int)hipErrorInvalidValue;
+  ((SkyFinishJob*)job)->nv = 0;
+  return attn_long_seg_bwd_dbias_impl(stream, qkv, dout, out, ids, bounds, m,
+                                      lsum, dot, dqkv, B, S, h, d, scale, keep,
+                                      salt, state, scratch, dbias, dbias_dt,
+                                      (SkyFinishJob*)job, true);
 }

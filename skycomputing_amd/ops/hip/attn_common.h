@@ -252,6 +252,38 @@ DEV void att_score_tile_t_range(f32x4 (&acc)[8], const bf16x8 (&b)[2],
   }
 }
 
+// ---- causal (triangle) mode of the keys-on-rows kernels ----
+// Query q attends key k iff k <= q. The additive values of a 128-token key
+// image's tile mt, four keys lg*4.., against the lane's own query at image
+// position rel (its token index minus the image's first key; >= 128 when the
+// whole image lies before the query): 0 for a key at or before the query,
+// -3e38 (the value of a key >= n, the image's valid count) otherwise. SEG:
+// the key must carry the lane's segment id as well, in the same select.
+template <bool SEG>
+DEV f32x4 att_tri_mask4(const int* sk, int mt, int lg, int own, int rel, int n) {
+  att_i32x4 id = {0, 0, 0, 0};
+  if constexpr (SEG) id = *(const att_i32x4*)(sk + mt * 16 + lg * 4);
+  f32x4 mv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int t = mt * 16 + lg * 4 + r;
+    mv[r] = (t <= rel && t < n && (!SEG || id[r] == own)) ? 0.f : -3.0e38f;
+  }
+  return mv;
+}
+// A wave's visible range [lo, hi) (att_seg_wave_range's, or [0, S) without
+// ids) cut to the triangle, as tiles t0..t1 and pairs p0..p1. base is the
+// first of the wave's 16 tokens, lo <= base < hi on entry. keys = true: the
+// wave holds queries and the range is of keys, everything before the end of
+// its own tile; keys = false: the wave holds keys and the range is of
+// queries, its own tile and upward. The diagonal tile stays inside.
+DEV void att_tri_range(int& t0, int& t1, int& p0, int& p1, int lo, int hi,
+                       int base, bool keys) {
+  if (keys) hi = hi < base + 16 ? hi : base + 16;
+  else lo = lo > base ? lo : base;
+  t0 = lo >> 4, t1 = (hi + 15) >> 4, p0 = lo >> 5, p1 = (hi + 31) >> 5;
+}
+
 // stage nrows rows of a [tok][64] bf16 row image (token stride tstride,
 // first token tok0) to LDS offset off via global_load_lds. The XOR swizzle
 // moves to the SOURCE address (lane-linear LDS image == sw7 layout). With

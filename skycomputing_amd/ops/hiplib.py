@@ -146,6 +146,16 @@ def _register_signatures(lib):
         "sky_attn_seg_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
         "sky_attn_seg_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
         "sky_attn_seg_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        # causal (q attends k iff k <= q): the argument lists of the segment
+        # forms above; ids (and bounds) may be 0 for "no packing"
+        "sky_attn_causal_fwd": [u64, u64, u64, u64, u64, u64, i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_causal_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_causal_bwd_dbias": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        "sky_attn_causal_bwd_dbias_parts": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        "sky_attn_long_causal_fwd": [u64] * 7 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_long_causal_bwd": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_long_causal_bwd_dbias": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
+        "sky_attn_long_causal_bwd_dbias_parts": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending

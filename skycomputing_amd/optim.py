@@ -427,7 +427,22 @@ def _masked_lm_loss(num_classes: int | None = None, ignore_index: int = -100,
     return loss_fn
 
 
-LOSSES = {"CrossEntropy": _classification_loss, "MaskedLM": _masked_lm_loss}
+def _causal_lm_loss(num_classes: int | None = None, ignore_index: int = -100,
+                    inplace_backward: bool = False):
+    def loss_fn(logits, labels):
+        # next-token targets: the logits at t against the token at t + 1, as
+        # shifted LABELS, so the [B, S, V] logits are neither sliced nor copied
+        targets = torch.full_like(labels, ignore_index)
+        targets[:, :-1] = labels[:, 1:]
+        return ops.softmax_cross_entropy(
+            logits, targets, ignore_index=ignore_index, num_classes=num_classes,
+            inplace_backward=inplace_backward)
+
+    return loss_fn
+
+
+LOSSES = {"CrossEntropy": _classification_loss, "MaskedLM": _masked_lm_loss,
+          "CausalLM": _causal_lm_loss}
 
 
 def build_loss(cfg: dict | None = None):
@@ -439,6 +454,13 @@ def build_loss(cfg: dict | None = None):
     ``"MaskedLM"`` takes ``num_classes`` (the vocabulary size; the logits'
     further columns are padding), ``ignore_index`` and ``inplace_backward``
     and calls ops.softmax_cross_entropy: the mean over the labelled tokens.
+    ``"CausalLM"`` takes the same three keys; its ``labels`` are the token
+    ids ``[B, S]`` themselves, with ``ignore_index`` at every position that
+    is no target (padding). The logits at position t are scored against the
+    label at t + 1 and the last position has no target. With packed
+    sequences the caller also sets ``ignore_index`` at each run's FIRST
+    token, which removes the target that would cross from one run into the
+    next.
 
     With microbatches the engines average these per-microbatch means, and
     scale each backward by 1/M. For MaskedLM the step loss is therefore the

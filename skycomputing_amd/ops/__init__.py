@@ -123,10 +123,14 @@ def _attention_causal(qkv, mask, dropout_p, training, segment_ids):
             raise ValueError("attention: give either mask or segment_ids, not both")
         if segment_ids.shape != (B, S) or segment_ids.is_floating_point():
             raise ValueError("segment_ids must be an integer tensor [B, S]")
-    if mask is None and qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64:
-        from .functions import FusedAttentionFn, attn_causal_enabled
+    if (mask is None and qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and (d == 64 or (d == 128 and segment_ids is None))):
+        from .functions import (
+            FusedAttentionFn, attn_causal_enabled, attn_d128_enabled,
+        )
 
-        if attn_causal_enabled(S) and _use_hip(qkv):
+        enabled = attn_causal_enabled if d == 64 else attn_d128_enabled
+        if enabled(S) and _use_hip(qkv):
             out = FusedAttentionFn.apply(qkv, None, 1.0 / math.sqrt(d), dropout_p,
                                          training, segment_ids, True)
             return out.reshape(B, S, h * d)
@@ -190,6 +194,16 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
     An additive mask next to causal is never served by the hand kernels. At
     S = 1 causal is the identity and the call takes the path it takes without.
 
+    Head dim 128 (GPU, bf16, 1 <= S <= 4096, a mask or none, or causal with
+    neither mask nor segment_ids): the chunked kernels of
+    ops/hip/attention_d128.hip, one family for every S, under the same
+    counter-RNG dropout contract, where functions.attn_d128_enabled selects
+    them: SKY_ATTN_D128=1 / 0, unset by the measurement of
+    profiles/r17_notes.md (128 <= S <= 2048); never under SKY_NO_FUSED_ATTN=1,
+    SKY_NO_FUSED_ATTN_BWD=1 or SKY_ATTN_FUSED_BWD=1. segment_ids at d = 128,
+    and every d = 128 call the switch leaves alone, go where other head dims
+    go: sdpa for causal and segment_ids, the batched-GEMM path otherwise.
+
     GPU fast path (bf16, d=64, S<=128): ONE fused MFMA kernel
     (FusedAttentionFn); 128 < S <= 4096: its chunked form where
     functions.attn_long_enabled selects it (256 <= S <= 512 by default,
@@ -225,6 +239,15 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
                 ~same, float("-inf"))
             ctx = eager.attention_context(q, k, v, dense, dropout_p, training)
         return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
+    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 128:
+        from .functions import FusedAttentionFn, attn_d128_enabled
+
+        # head dim 128: the chunked kernels of ops/hip/attention_d128.hip at
+        # every 1 <= S <= 4096 where SKY_ATTN_D128 or the measured default
+        # selects them; otherwise the paths below, as before
+        if attn_d128_enabled(S) and _use_hip(qkv):
+            out = FusedAttentionFn.apply(qkv, mask, scale, dropout_p, training)
+            return out.reshape(B, S, h * d)
     if (
         qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 64
         and hiplib.available() and os.environ.get("SKY_NO_FUSED_ATTN") != "1"
@@ -325,7 +348,8 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     (functions.attn_seg_enabled), with the dropout mask of the project's
     counter RNG. causal (ops.attention) takes the node with mask = None
     wherever functions.attn_causal_enabled selects the hand kernels.
-    Everything else — CPU, fp32, long sequences,
+    Everything else — CPU, fp32, long sequences, head dim 128 (whose
+    ops.attention reaches the d = 128 hand kernels, functions.attn_d128_enabled),
     SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
     paths — is the composition of ops.linear, ops.attention and
     ops.linear_residual_layer_norm."""

@@ -392,6 +392,34 @@ def attn_causal_enabled(S: int) -> bool:
             and _ATTN_CAUSAL_DEFAULT[0] < S <= _ATTN_CAUSAL_DEFAULT[1])
 
 
+# Head dim 128 (ops/hip/attention_d128.hip). SKY_ATTN_D128 unset: the (lo, hi]
+# range of S at which ops.attention runs the d = 128 hand kernels by default:
+# 128 <= S <= 2048. At S = 128, 512 and 2048 (h = 8, 4096 tokens, bf16,
+# p = 0.1) their forward + backward median was below sdpa's with
+# non-overlapping ranges in both runs, with the additive mask (128 / 63
+# against 176 / 173, 127 against 281, 396 / 391 against 738 us) and causal
+# (128 / 64 against 195 / 193, 133 against 251, 428 / 427 against 617 us;
+# profiles/r17_notes.md). Below 128 and above 2048 nothing was measured and
+# the call goes where it went before; SKY_ATTN_D128=1 opts in.
+ATTN_D128 = 128
+_ATTN_D128_DEFAULT = (127, 2048)
+
+
+def attn_d128_enabled(S: int) -> bool:
+    """Whether ops.attention runs the head-dim-128 hand kernels at this S,
+    1 <= S <= 4096 (causal: 2 <= S, the caller's condition): SKY_ATTN_D128=1
+    / 0 forces it, unset by measurement. Never under SKY_NO_FUSED_ATTN=1,
+    SKY_NO_FUSED_ATTN_BWD=1 or SKY_ATTN_FUSED_BWD=1."""
+    if not 1 <= S <= ATTN_LONG_SMAX or any(os.environ.get(v) == "1" for v in (
+            "SKY_NO_FUSED_ATTN", "SKY_NO_FUSED_ATTN_BWD", "SKY_ATTN_FUSED_BWD")):
+        return False
+    e = os.environ.get("SKY_ATTN_D128")
+    if e in ("0", "1"):
+        return e == "1"
+    return (_ATTN_D128_DEFAULT is not None
+            and _ATTN_D128_DEFAULT[0] < S <= _ATTN_D128_DEFAULT[1])
+
+
 def _attn_seg(segment_ids):
     """Segment ids as the kernels take them: (int32 ids,) for S <= 128, where
     the kernels find their ranges from the ids, (ids, bounds) above."""
@@ -422,7 +450,8 @@ def _attn_fwd(qkv, mask, scale, keep, seg=None, causal=False):
     (out [B, S, h, d], m, lsum, salt). seg (_attn_seg): the segment form,
     sky_attn_long_seg_fwd on (ids, bounds) or sky_attn_seg_fwd on (ids,).
     causal: sky_attn_long_causal_fwd / sky_attn_causal_fwd, with or without
-    seg."""
+    seg. d = 128 (no seg): sky_attn_d128_fwd / sky_attn_d128_causal_fwd at
+    every S; the causal entry takes no mask pointer at all."""
     lib = hiplib.require()
     B, S, _, h, d = qkv.shape
     out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
@@ -430,7 +459,10 @@ def _attn_fwd(qkv, mask, scale, keep, seg=None, causal=False):
     lsum = torch.empty_like(m)
     salt = _next_seed() if keep < 1.0 else 0
     state = rng_state()
-    if causal:
+    if d == ATTN_D128:
+        name = "sky_attn_d128_causal_fwd" if causal else "sky_attn_d128_fwd"
+        masks = () if causal else (ptr(mask),)
+    elif causal:
         long_ = S > ATTN_SMAX
         name = "sky_attn_long_causal_fwd" if long_ else "sky_attn_causal_fwd"
         masks = _attn_ids(seg, 2 if long_ else 1)
@@ -490,7 +522,11 @@ class FusedAttentionFn(torch.autograd.Function):
     SKY_NO_FUSED_ATTN_BWD=1 selects the decomposed fallback (sky_attn_probs
     recompute + hipBLASLt batched GEMMs + HIP softmax-backward).
 
-    qkv: [B, S, 3, h, d] (d = 64), mask: [B, 1, 1, S] additive or None.
+    qkv: [B, S, 3, h, d] (d = 64 or 128), mask: [B, 1, 1, S] additive or
+    None. d = 128 (1 <= S <= 4096, mask or causal, no segment_ids): the
+    chunked kernels of ops/hip/attention_d128.hip at every S; out is saved
+    for the backward, whose dQ kernel takes the row dots from dO * O, and the
+    fp32 row dots [B*h*S] are the only scratch.
     segment_ids (packed sequences, 2 <= S <= 4096, no mask): integer
     [B, S], q attends k iff their ids are equal; equal ids must form one
     contiguous run per row, which is NOT checked here (a check would
@@ -510,7 +546,8 @@ class FusedAttentionFn(torch.autograd.Function):
     def forward(ctx, qkv, mask, scale, dropout_p, training, segment_ids=None,
                 causal=False):
         B, S, three, h, d = qkv.shape
-        assert three == 3 and d == 64 and S <= ATTN_LONG_SMAX
+        assert three == 3 and d in (64, ATTN_D128) and S <= ATTN_LONG_SMAX
+        assert d == 64 or segment_ids is None
         qkv = qkv.contiguous()
         mask = mask.contiguous() if mask is not None else None
         keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
@@ -521,7 +558,7 @@ class FusedAttentionFn(torch.autograd.Function):
             seg = _attn_seg(segment_ids)
         out, m, lsum, salt = _attn_fwd(qkv, mask, scale, keep, seg or None, causal)
         # the long backward takes its row dots from dO * O
-        extra = (out,) if S > ATTN_SMAX else ()
+        extra = (out,) if S > ATTN_SMAX or d == ATTN_D128 else ()
         ctx.save_for_backward(qkv, mask, m, lsum, *extra, *seg)
         ctx.scale, ctx.keep, ctx.salt, ctx.causal = scale, keep, salt, causal
         return out
@@ -532,6 +569,20 @@ class FusedAttentionFn(torch.autograd.Function):
         qkv, mask, m, lsum, *extra = ctx.saved_tensors
         B, S, _, h, d = qkv.shape
         dev = qkv.device
+        if d == ATTN_D128:
+            # dQ + dot, then dK/dV (ops/hip/attention_d128.hip), every S
+            dout = dout.contiguous()
+            dqkv = torch.empty_like(qkv)
+            dot = torch.empty(B * h * S, dtype=torch.float32, device=dev)
+            args = _attn_long_bwd_args(
+                qkv, dout, extra[0], mask, m, lsum, dot, dqkv, ctx.scale,
+                ctx.keep, ctx.salt)
+            if ctx.causal:  # no mask pointer
+                check(lib.sky_attn_d128_causal_bwd(*args[:4], *args[5:]),
+                      "sky_attn_d128_causal_bwd")
+            else:
+                check(lib.sky_attn_d128_bwd(*args), "sky_attn_d128_bwd")
+            return dqkv, None, None, None, None, None, None
         if S > ATTN_SMAX:
             # dQ + dot, then dK/dV (ops/hip/attention_long.hip); the env
             # switches below select among the S <= 128 kernels only

@@ -15,6 +15,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define ATT_SMAX 128
 #define ATT_D 64
+#define ATT_D128 128  // the head dim of attention_d128.hip
 
 // LDS layout shared by the keys-on-rows kernels: two [128][64] sw7 row
 // images (K | V in the forward and the dQ kernel, Q | dO in the dK/dV
@@ -95,6 +96,23 @@ DEV bf16x8 abf_tr_rows128(const char* lds_base, int off, int r0, int cq0,
                   v[1][0], v[1][1], v[1][2], v[1][3]};
 }
 
+// abf_tr_rows64_2 for a [64 tok][128] sw15 image (d = 128, 256-B rows): the
+// A operand that goes with att_pack_dpair, regs j = 0..3 image rows ra..,
+// regs j = 4..7 image rows rb.., output columns cq0*4 .. cq0*4 + 15
+DEV bf16x8 abf_tr_rows128_2(const char* lds_base, int off, int ra, int rb,
+                            int cq0, int s4) {
+  s16x4_a v[2];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int row = (half ? rb : ra) + (s4 >> 2);
+    const int byte = (off + row * 256 + (cq0 + (s4 & 3)) * 8) ^ ((row & 15) << 4);
+    v[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (abf_las4)(lds_base + byte));
+  }
+  return (bf16x8){v[0][0], v[0][1], v[0][2], v[0][3],
+                  v[1][0], v[1][1], v[1][2], v[1][3]};
+}
+
 template <int N> DEV void att_zero(f32x4 (&acc)[N]) {
 #pragma unroll
   for (int i = 0; i < N; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -163,6 +181,28 @@ DEV void att_score_tile_t(f32x4 (&acc)[8], const bf16x8 (&b)[2], char* lds,
       bf16x8 at = *(const bf16x8*)lds_at(
           lds, swz(off + tok * 128 + (ks * 32 + lg * 8) * 2, tok, 7));
       acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at, b[ks], acc[mt], 0, 0, 0);
+    }
+  }
+}
+
+// the d = 128 form: N adjacent transposed score tiles tbase.. of a
+// [64 tok][128] sw15 image, four contraction steps of 32 each against the
+// wave's fragment quad b. Only tiles t0 <= tbase + i < t1 are visited; the
+// other accumulators keep what they hold (the callers' zeros).
+template <int N>
+DEV void att_score_tile_t128(f32x4 (&acc)[N], const bf16x8 (&b)[4], char* lds,
+                             int off, int tbase, int t0, int t1, int lm,
+                             int lg) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int mt = tbase + i;
+    if (mt < t0 || mt >= t1) continue;
+    const int tok = mt * 16 + lm;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      bf16x8 at = *(const bf16x8*)lds_at(
+          lds, swz(off + tok * 256 + (ks * 32 + lg * 8) * 2, tok, 15));
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at, b[ks], acc[i], 0, 0, 0);
     }
   }
 }
@@ -295,6 +335,22 @@ DEV void att_glds_rows(const ushort_t* src, int tstride, int tok0, int nrows,
     int gtok = tok0 + tok;
     if (clamp && gtok >= S) gtok = S - 1;
     const int c16s = (u & 7) ^ (tok & 7);  // pre-swizzled source column
+    __builtin_amdgcn_global_load_lds(
+        (att_gas)(src + (size_t)gtok * tstride + c16s * 8),
+        (att_las)lds_at(lds, off + u * 16), 16, 0, 0);
+  }
+}
+
+// the same for 256-B rows (d = 128): nrows rows of a [tok][128] bf16 row
+// image, 16 lanes per row, lane-linear LDS image == sw15 layout. nrows is a
+// multiple of 16, so whole waves load. Tokens >= S re-read token S-1.
+DEV void att_glds_rows128(const ushort_t* src, int tstride, int tok0,
+                          int nrows, int S, char* lds, int off, int tid) {
+  for (int u = tid; u < nrows * 16; u += 256) {
+    const int tok = u >> 4;
+    int gtok = tok0 + tok;
+    if (gtok >= S) gtok = S - 1;
+    const int c16s = (u & 15) ^ (tok & 15);  // pre-swizzled source column
     __builtin_amdgcn_global_load_lds(
         (att_gas)(src + (size_t)gtok * tstride + c16s * 8),
         (att_las)lds_at(lds, off + u * 16), 16, 0, 0);
@@ -466,6 +522,18 @@ DEV void att_store_cols16(ushort_t* __restrict__ dst, int rstride,
   if (row >= S) return;
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct)
+    *(ushort4_t*)(dst + (size_t)row * rstride + ct * 16 + lg * 4) =
+        f32x4_to_bf16x4(acc[ct][0], acc[ct][1], acc[ct][2], acc[ct][3]);
+}
+
+// the same for a 128-col x 16-row tile (d = 128), eight f32x4 per lane
+DEV void att_store_cols16_d128(ushort_t* __restrict__ dst, int rstride,
+                               const f32x4 (&acc)[8], int row0, int S, int lm,
+                               int lg) {
+  const int row = row0 + lm;
+  if (row >= S) return;
+#pragma unroll
+  for (int ct = 0; ct < 8; ++ct)
     *(ushort4_t*)(dst + (size_t)row * rstride + ct * 16 + lg * 4) =
         f32x4_to_bf16x4(acc[ct][0], acc[ct][1], acc[ct][2], acc[ct][3]);
 }

@@ -156,6 +156,15 @@ def _register_signatures(lib):
         "sky_attn_long_causal_bwd": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64],
         "sky_attn_long_causal_bwd_dbias": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32],
         "sky_attn_long_causal_bwd_dbias_parts": [u64] * 10 + [i64, i64, i64, i64, f32, f32, u64, u64, u64, u64, i32, u64],
+        # head dim 128, 1 <= S <= 4096 (ops/hip/attention_d128.hip): the
+        # argument lists of sky_attn_long_fwd / sky_attn_long_bwd; the causal
+        # pair takes neither mask nor ids nor bounds
+        "sky_attn_d128_fwd": [u64] * 6 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_d128_bwd": [u64] * 9 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_d128_causal_fwd": [u64] * 5 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        # strm qkv out m l | B S h d scale keep salt state
+        "sky_attn_d128_causal_bwd": [u64] * 8 + [i64, i64, i64, i64, f32, f32, u64, u64],
+        # strm qkv dout out m l dot dqkv | B S h d scale keep salt state
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending

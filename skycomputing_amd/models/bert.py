@@ -27,6 +27,7 @@ class BertConfig:
         layer_norm_eps: float = 1e-12,
         output_all_encoded_layers: bool = False,
         causal: bool = False,
+        num_key_value_heads: int | None = None,
     ):
         if isinstance(vocab_size_or_config_json_file, str):
             with open(vocab_size_or_config_json_file) as f:
@@ -49,6 +50,9 @@ class BertConfig:
         self.output_all_encoded_layers = output_all_encoded_layers
         # decoder-only (GPT-style) stacks: every attention layer is causal
         self.causal = causal
+        # grouped-query attention: the key / value heads the query heads
+        # share (a divisor of num_attention_heads); None: multi-head
+        self.num_key_value_heads = num_key_value_heads
 
     @classmethod
     def from_dict(cls, d: dict) -> "BertConfig":

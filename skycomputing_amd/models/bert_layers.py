@@ -111,15 +111,30 @@ class BertSelfAttention(nn.Module):
         self.num_heads = config.num_attention_heads
         self.head_dim = config.hidden_size // config.num_attention_heads
         H = config.hidden_size
-        self.qkv = SkyLinear(H, 3 * H)
+        # config key num_key_value_heads (None: multi-head): grouped-query
+        # attention, h query heads on h_kv key / value heads, and a qkv
+        # projection of (h + 2*h_kv) heads (ops.attention, num_kv_heads)
+        self.num_kv_heads = getattr(config, "num_key_value_heads", None)
+        if self.num_kv_heads is None:
+            self.qkv = SkyLinear(H, 3 * H)
+        else:
+            if not (1 <= self.num_kv_heads <= self.num_heads
+                    and self.num_heads % self.num_kv_heads == 0):
+                raise ValueError("num_attention_heads must be a multiple of num_key_value_heads")
+            self.qkv = SkyLinear(H, (self.num_heads + 2 * self.num_kv_heads) * self.head_dim)
         self.dropout_p = config.attention_probs_dropout_prob
         self.causal = bool(getattr(config, "causal", False))
 
     def forward(self, hidden, ext_mask):
         B, S, H = hidden.shape
-        qkv = self.qkv(hidden).view(B, S, 3, self.num_heads, self.head_dim)
+        if self.num_kv_heads is None:
+            qkv = self.qkv(hidden).view(B, S, 3, self.num_heads, self.head_dim)
+        else:
+            qkv = self.qkv(hidden).view(
+                B, S, self.num_heads + 2 * self.num_kv_heads, self.head_dim)
         mask, ids = _causal_masks(ext_mask, self.causal)
-        return ops.attention(qkv, mask, self.dropout_p, self.training, ids, self.causal)
+        return ops.attention(qkv, mask, self.dropout_p, self.training, ids,
+                             self.causal, self.num_kv_heads)
 
 
 def _causal_masks(ext_mask, causal: bool):
@@ -236,13 +251,16 @@ class BertLayerHead(nn.Module):
             hidden, mask, att.qkv.weight,
             att.qkv.bias, att.num_heads, att.dropout_p, out.dense.weight, out.dense.bias,
             out.layer_norm.weight, out.layer_norm.bias, out.layer_norm.eps,
-            out.dropout_p, self.training, ids, att.causal)
+            out.dropout_p, self.training, ids, att.causal, att.num_kv_heads)
         return y, ext_mask
 
     def layer_flops(self, batch: int, seq: int) -> float:
         H = self.config.hidden_size
         # QKV + output projections: 4 GEMMs of [B*S,H]x[H,H]; attention 2 batched GEMMs
         gemm = 4 * 2.0 * batch * seq * H * H
+        if self.attention.num_kv_heads is not None:
+            # grouped-query: the K and V projections are h_kv / h as wide
+            gemm = 2.0 * batch * seq * H * (self.attention.qkv.weight.shape[0] + H)
         attn = 2 * 2.0 * batch * self.config.num_attention_heads * seq * seq * (
             H // self.config.num_attention_heads
         )
@@ -415,7 +433,9 @@ def bert_pretraining_pipeline_config(
     bert_config: dict | None = None,
 ) -> list[dict]:
     """The layer-config list of an N-encoder-layer BERT with the masked-LM
-    head: embeddings, N x (Head, Body, Tail), BertLMHead."""
+    head: embeddings, N x (Head, Body, Tail), BertLMHead. bert_config keys
+    reach every layer: num_key_value_heads there makes each attention
+    grouped-query (BertSelfAttention)."""
     bc = dict(bert_config or {})
     layers: list[dict] = [dict(layer_type="BertEmbeddings", config=bc)]
     for _ in range(num_encoder_layers):

@@ -157,10 +157,48 @@ def _attention_causal(qkv, mask, dropout_p, training, segment_ids):
     return ctx.permute(0, 2, 1, 3).reshape(B, S, h * d)
 
 
+def _attention_gqa(qkv, mask, dropout_p, training, segment_ids, causal,
+                   num_kv_heads):
+    """ops.attention with num_kv_heads given (see there)."""
+    if qkv.dim() != 4:
+        raise ValueError("attention: with num_kv_heads qkv is [B, S, h + 2*h_kv, d]")
+    B, S, heads, d = qkv.shape
+    h = heads - 2 * num_kv_heads
+    if num_kv_heads < 1 or h < num_kv_heads or h % num_kv_heads != 0:
+        raise ValueError(
+            f"attention: {h} query heads cannot share {num_kv_heads} key/value heads")
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 128
+            and segment_ids is None and not (causal and mask is not None)):
+        from .functions import FusedGqaAttentionFn, attn_gqa_enabled
+
+        tri = causal and S > 1  # the identity at S = 1
+        if attn_gqa_enabled(S) and _use_hip(qkv):
+            out = FusedGqaAttentionFn.apply(
+                qkv, mask, num_kv_heads, 1.0 / math.sqrt(d), dropout_p, training, tri)
+            return out.reshape(B, S, h * d)
+    return attention(eager.expand_kv(qkv, num_kv_heads), mask, dropout_p,
+                     training, segment_ids, causal)
+
+
 def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
-              segment_ids=None, causal: bool = False):
+              segment_ids=None, causal: bool = False, num_kv_heads=None):
     """Multi-head attention over a packed qkv tensor [B, S, 3, h, d];
     returns [B, S, h*d].
+
+    num_kv_heads (grouped-query attention, None: multi-head): qkv is
+    [B, S, h + 2*h_kv, d] instead, the h query heads, then the h_kv key
+    heads, then the h_kv value heads, and query head hh attends key / value
+    head hh // (h // h_kv); ValueError for a 5-D qkv, h < h_kv or
+    h % h_kv != 0. GPU, bf16, d = 128, 1 <= S <= 4096, a mask or none, or
+    causal with neither mask nor segment_ids: FusedGqaAttentionFn on the
+    grouped-query forms of the d = 128 kernels (the dK/dV kernel sums a
+    group's heads in registers; the keep mask is the multi-head kernels' for
+    the same h) where functions.attn_gqa_enabled selects them: SKY_ATTN_GQA=1
+    / 0, unset off (profiles/r18_notes.md); never under SKY_NO_FUSED_ATTN=1,
+    SKY_NO_FUSED_ATTN_BWD=1 or SKY_ATTN_FUSED_BWD=1. Every other call (CPU,
+    fp32, d = 64, segment_ids, a mask next to causal, the switch off) expands
+    K and V to h heads (eager.expand_kv, whose backward sums the group's
+    gradients) and goes where multi-head attention of that shape goes.
 
     segment_ids (packed sequences): integer [B, S] in the place of mask;
     query q attends key k iff segment_ids[b, q] == segment_ids[b, k]. Equal
@@ -212,6 +250,9 @@ def attention(qkv, mask, dropout_p: float = 0.0, training: bool = False,
     CPU)."""
     from .functions import _split_heads
 
+    if num_kv_heads is not None:
+        return _attention_gqa(qkv, mask, dropout_p, training, segment_ids,
+                              causal, num_kv_heads)
     B, S, three, h, d = qkv.shape
     scale = 1.0 / math.sqrt(d)
     if causal and S > 1:
@@ -333,7 +374,7 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
                     attn_dropout_p: float, out_weight, out_bias, ln_weight,
                     ln_bias, eps: float = 1e-12, hidden_dropout_p: float = 0.0,
                     training: bool = False, segment_ids=None,
-                    causal: bool = False):
+                    causal: bool = False, num_kv_heads=None):
     """The attention third of an encoder block:
     LN(dropout(attention(hidden @ Wqkv^T + bqkv) @ Wo^T + bo) + hidden)
     for hidden [B, S, H], mask [B, 1, 1, S] additive or None.
@@ -352,9 +393,21 @@ def attention_block(hidden, mask, qkv_weight, qkv_bias, num_heads: int,
     ops.attention reaches the d = 128 hand kernels, functions.attn_d128_enabled),
     SKY_NO_ATTN_BLOCK=1, SKY_NO_LN_DBIAS=1 and the env-selected attention
     paths — is the composition of ops.linear, ops.attention and
-    ops.linear_residual_layer_norm."""
+    ops.linear_residual_layer_norm.
+
+    num_kv_heads (grouped-query attention, ops.attention): qkv_weight is
+    [(h + 2*h_kv)*d, H] and the call is always that composition, on the 4-D
+    packed view; AttentionBlockFn is head dim 64 multi-head attention only."""
     B, S, H = hidden.shape
     d = H // num_heads
+    if num_kv_heads is not None:
+        qkv = linear(hidden, qkv_weight, qkv_bias).view(
+            B, S, num_heads + 2 * num_kv_heads, d)
+        attn = attention(qkv, mask, attn_dropout_p, training, segment_ids,
+                         causal, num_kv_heads)
+        return linear_residual_layer_norm(
+            attn, out_weight, out_bias, ln_weight, ln_bias, eps, hidden,
+            hidden_dropout_p, training)
     causal = causal and S > 1  # the identity at S = 1
     # ids the node cannot take (next to a mask, wrong shape or type) go to
     # ops.attention, which raises for them

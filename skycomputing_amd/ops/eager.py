@@ -90,6 +90,19 @@ def attention_context(
     return torch.matmul(probs, v)
 
 
+def expand_kv(qkv: torch.Tensor, num_kv_heads: int) -> torch.Tensor:
+    """The multi-head tensor [B, S, 3, h, d] of a grouped-query packed qkv
+    [B, S, h + 2*h_kv, d] (query heads, then key heads, then value heads):
+    every key / value head repeated for the G = h / h_kv query heads of its
+    group, so that query head hh meets K/V head hh // G. Differentiable: the
+    backward sums a group's dK and dV."""
+    h = qkv.shape[2] - 2 * num_kv_heads
+    q, k, v = qkv.split((h, num_kv_heads, num_kv_heads), dim=2)
+    G = h // num_kv_heads
+    return torch.stack(
+        (q, k.repeat_interleave(G, dim=2), v.repeat_interleave(G, dim=2)), dim=2)
+
+
 def seg_runs(segment_ids: torch.Tensor):
     """Per token of integer ids [B, S]: the start and the (exclusive) end of
     its run of equal neighbours, two int64 [B, S]."""

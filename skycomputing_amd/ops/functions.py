@@ -420,6 +420,38 @@ def attn_d128_enabled(S: int) -> bool:
             and _ATTN_D128_DEFAULT[0] < S <= _ATTN_D128_DEFAULT[1])
 
 
+# Grouped-query attention at head dim 128 (FusedGqaAttentionFn). SKY_ATTN_GQA
+# unset: the (lo, hi] range of S at which ops.attention(num_kv_heads=) runs
+# the sky_attn_d128_gqa_* kernels by default; None: nowhere, which is what
+# the measurement gave (profiles/r18_notes.md; MI355X, 4096 tokens, h = 8,
+# h_kv = 2 and 1, bf16, p = 0.1, forward + backward, against expand_kv + the
+# multi-head d = 128 kernels and against sdpa(enable_gqa=True), mask and
+# causal, two runs). S = 128: 73 / 103 us (h_kv = 2 / 1) against 145 / 143 us
+# expanded, but one of the eight comparisons (h_kv = 1, causal, run 1) had
+# overlapping ranges, 108.6 to 143.8 against 143.0 to 159.8, so the length
+# does not meet the rule. S = 512: level at h_kv = 2 (206 against 206 us),
+# slower at h_kv = 1 (332 against 236 / 208). S = 2048: slower, 738 / 1239
+# against 470 / 482 us: the dK/dV grid is B * h_kv * ceil(S/64) blocks of G
+# times the work, 128 or 64 blocks on 256 CUs there. SKY_ATTN_GQA=1 opts in.
+_ATTN_GQA_DEFAULT = None
+
+
+def attn_gqa_enabled(S: int) -> bool:
+    """Whether ops.attention(num_kv_heads=) runs the grouped-query hand
+    kernels at this S, 1 <= S <= 4096 (causal: 2 <= S, the caller's
+    condition): SKY_ATTN_GQA=1 / 0 forces it, unset by measurement. Never
+    under SKY_NO_FUSED_ATTN=1, SKY_NO_FUSED_ATTN_BWD=1 or
+    SKY_ATTN_FUSED_BWD=1."""
+    if not 1 <= S <= ATTN_LONG_SMAX or any(os.environ.get(v) == "1" for v in (
+            "SKY_NO_FUSED_ATTN", "SKY_NO_FUSED_ATTN_BWD", "SKY_ATTN_FUSED_BWD")):
+        return False
+    e = os.environ.get("SKY_ATTN_GQA")
+    if e in ("0", "1"):
+        return e == "1"
+    return (_ATTN_GQA_DEFAULT is not None
+            and _ATTN_GQA_DEFAULT[0] < S <= _ATTN_GQA_DEFAULT[1])
+
+
 def _attn_seg(segment_ids):
     """Segment ids as the kernels take them: (int32 ids,) for S <= 128, where
     the kernels find their ranges from the ids, (ids, bounds) above."""
@@ -668,6 +700,72 @@ class FusedAttentionFn(torch.autograd.Function):
             return dPd
 
         dqkv = _attn_bwd_decomposed(qkv, P, Pd, dout, ctx.scale, dP_of)
+        return dqkv, None, None, None, None, None, None
+
+
+class FusedGqaAttentionFn(torch.autograd.Function):
+    """Grouped-query attention at head dim 128 (bf16, 1 <= S <= 4096, causal:
+    2 <= S): h query heads on h_kv shared key / value heads, the
+    sky_attn_d128_gqa_* entry points of ops/hip/attention_d128.hip.
+
+    qkv: [B, S, h + 2*h_kv, 128], query heads, then key heads, then value
+    heads; query head hh attends K/V head hh // (h // h_kv). mask:
+    [B, 1, 1, S] additive or None; causal takes no mask. Forward and dQ run
+    one block per query head on the shared K/V columns; the dK/dV kernel
+    runs one block per K/V head and sums the group's heads in its registers,
+    so dqkv holds each shared head's gradient rounded once. Saves qkv, mask,
+    m, l and out; the fp32 row dots [B*h*S] are the only scratch. Dropout
+    draws by the query head, so for equal (salt, state, B, S, h) the keep
+    mask is FusedAttentionFn's on the expanded heads. Returns [B, S, h, 128].
+    """
+
+    @staticmethod
+    def forward(ctx, qkv, mask, num_kv_heads, scale, dropout_p, training,
+                causal=False):
+        lib = hiplib.require()
+        B, S, heads, d = qkv.shape
+        h = heads - 2 * num_kv_heads
+        assert d == ATTN_D128 and 1 <= num_kv_heads <= h and h % num_kv_heads == 0
+        assert S <= ATTN_LONG_SMAX and (not causal or (mask is None and S >= 2))
+        qkv = qkv.contiguous()
+        mask = mask.contiguous() if mask is not None else None
+        keep = 1.0 - dropout_p if (dropout_p > 0 and training) else 1.0
+        out = torch.empty(B, S, h, d, dtype=qkv.dtype, device=qkv.device)
+        m = torch.empty(B, h, S, dtype=torch.float32, device=qkv.device)
+        lsum = torch.empty_like(m)
+        salt = _next_seed() if keep < 1.0 else 0
+        name = "sky_attn_d128_gqa_causal_fwd" if causal else "sky_attn_d128_gqa_fwd"
+        masks = () if causal else (ptr(mask),)  # the causal entry takes no mask
+        check(
+            getattr(lib, name)(
+                _stream(), ptr(qkv), *masks, ptr(out), ptr(m), ptr(lsum), B, S,
+                h, num_kv_heads, d, scale, keep, salt, rng_state().data_ptr(),
+            ),
+            name,
+        )
+        ctx.save_for_backward(qkv, mask, m, lsum, out)
+        ctx.h_kv, ctx.scale, ctx.keep = num_kv_heads, scale, keep
+        ctx.salt, ctx.causal = salt, causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = hiplib.require()
+        qkv, mask, m, lsum, out = ctx.saved_tensors
+        B, S, h, d = out.shape
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        dot = torch.empty(B * h * S, dtype=torch.float32, device=qkv.device)
+        name = "sky_attn_d128_gqa_causal_bwd" if ctx.causal else "sky_attn_d128_gqa_bwd"
+        masks = () if ctx.causal else (ptr(mask),)
+        check(
+            getattr(lib, name)(
+                _stream(), ptr(qkv), ptr(dout), ptr(out), *masks, ptr(m),
+                ptr(lsum), ptr(dot), ptr(dqkv), B, S, h, ctx.h_kv, d, ctx.scale,
+                ctx.keep, ctx.salt, rng_state().data_ptr(),
+            ),
+            name,
+        )
         return dqkv, None, None, None, None, None, None
 
 

@@ -34,6 +34,20 @@
 // (mask / no mask / causal; no AGPRs; LDS is dynamic, the launch's figure;
 // profiles/r17_notes.md has the same table.)
 //
+// Grouped-query attention (template parameter GQA, sky_attn_d128_gqa_*): h
+// query heads on h_kv shared K/V heads over the packed layout
+// [B, S, h + 2*h_kv, 128] (AtdHeads). Forward and dQ: a block per query head
+// as above, only the K/V base pointers and the token stride differ. dK/dV: a
+// block per (b, K/V head, 64-key block) walks the group's G = h / h_kv query
+// heads one after the other into the same dK^T and dV^T registers (see the
+// kernel). The GQA = false instantiations are the figures above; GQA = true:
+//   attn_d128_fwd_kernel     106 / 107 / 108 VGPRs, LDS 33280 B, 4 waves/SIMD
+//   attn_d128_bwd_dq_kernel  128 / 128 / 128 VGPRs, LDS 33280 B, 4 waves/SIMD
+//   attn_d128_bwd_dkv_kernel 164 / 164 / 165 VGPRs, LDS 34560 B, 3 waves/SIMD
+// scratch 0, no AGPRs; the dK/dV kernel keeps 14 / 14 / 8 scalars in lanes of
+// one VGPR, read once per head outside the chunk walk
+// (profiles/r18_notes.md).
+//
 // Dropout: att_drop_hash_c64 + att_drop_keep (attn_common.h), index
 // ((bh*S + row)*16 + key%16) * NC + key/64, slice (key/16) & 3: no d in it, so
 // for equal (salt, state, B, S, h) the keep mask is the d = 64 long kernels'
@@ -101,6 +115,22 @@ DEV float atd_row_dot(const ushort_t* __restrict__ orow,
   return __shfl(dsel, ((lm >> 2) << 4) | lm, 64);
 }
 
+// The head arithmetic of the packed layout [B, S, h + 2*h_kv, 128]: query
+// head hh at column hh, key head g at h + g, value head g at h + h_kv + g
+// (columns of 128 values), query head hh on K/V head hh / G, G = h / h_kv.
+// GQA = false is multi-head attention, [B, S, 3, h, 128]: h_kv is not read
+// and every expression folds to the one in h alone. All of it is computed
+// from kernel arguments and the block index: wave-uniform scalars.
+template <bool GQA>
+struct AtdHeads {
+  int h, hkv, G, ts;
+  DEV AtdHeads(int h_, int h_kv)
+      : h(h_), hkv(GQA ? h_kv : h_), G(GQA ? h_ / h_kv : 1),
+        ts((h_ + 2 * (GQA ? h_kv : h_)) * ATT_D128) {}
+  DEV int kcol(int g) const { return h + g; }
+  DEV int vcol(int g) const { return h + hkv + g; }
+};
+
 // LDS of the forward and the dQ kernel: K chunk @0, V chunk @16K, the
 // chunk's key mask fp32 @32K (att_mask_keys_lds_at writes 128 values, the
 // chunk's 64 and the next chunk's): 33280 B, four blocks per CU,
@@ -115,12 +145,12 @@ DEV float atd_row_dot(const ushort_t* __restrict__ orow,
 // fragments from global, four bf16x8).
 // CAUSAL (no additive mask): q sees k iff k <= q. Block qb stops at chunk qb,
 // its diagonal chunk; inside it wave w stops at tile w, its own.
-template <bool HAS_MASK, bool CAUSAL>
+template <bool HAS_MASK, bool CAUSAL, bool GQA>
 ATD_KERNEL void attn_d128_fwd_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ mask,
     ushort_t* __restrict__ out, float* __restrict__ m_io,
     float* __restrict__ l_io, int B, int S, int h, float scale, float keep,
-    uint64_t salt, const unsigned long long* __restrict__ state) {
+    uint64_t salt, const unsigned long long* __restrict__ state, int h_kv) {
   static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
@@ -133,14 +163,16 @@ ATD_KERNEL void attn_d128_fwd_kernel(
   const int qb = blockIdx.x % QB;
   const int b = bh / h;
   const int hh = bh % h;
-  const int ts = 3 * h * ATT_D128;
+  const AtdHeads<GQA> hd(h, h_kv);
+  const int ts = hd.ts;
   const uint64_t seed = rng_seed(salt, state);
   const float inv_keep = 1.f / keep;
   const unsigned keep16 = keep_to_16(keep);
 
-  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D128;
-  const ushort_t* kbase = qbase + (size_t)h * ATT_D128;
-  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D128;
+  const ushort_t* tokb = qkv + (size_t)b * S * ts;
+  const ushort_t* qbase = tokb + (size_t)hh * ATT_D128;
+  const ushort_t* kbase = tokb + (size_t)hd.kcol(hh / hd.G) * ATT_D128;
+  const ushort_t* vbase = tokb + (size_t)hd.vcol(hh / hd.G) * ATT_D128;
   float* mk = (float*)lds_at(lds, ATD_MASK_OFF);
 
   const int qtok_base = qb * ATD_C + w * 16;
@@ -275,14 +307,14 @@ ATD_KERNEL void attn_d128_fwd_kernel(
 // each per tile), P from the saved statistics, dS^T over the scores,
 // dQ^T += K^T dS^T; only the pair is live. Writes dot[bh*S + q] for the
 // dK/dV kernel. LDS as the forward.
-template <bool HAS_MASK, bool CAUSAL>
+template <bool HAS_MASK, bool CAUSAL, bool GQA>
 ATD_KERNEL void attn_d128_bwd_dq_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ out, const ushort_t* __restrict__ mask,
     const float* __restrict__ m_io, const float* __restrict__ l_io,
     float* __restrict__ dot_out, ushort_t* __restrict__ dqkv, int B, int S,
     int h, float scale, float keep, uint64_t salt,
-    const unsigned long long* __restrict__ state) {
+    const unsigned long long* __restrict__ state, int h_kv) {
   static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
@@ -295,15 +327,17 @@ ATD_KERNEL void attn_d128_bwd_dq_kernel(
   const int qb = blockIdx.x % QB;
   const int b = bh / h;
   const int hh = bh % h;
-  const int ts = 3 * h * ATT_D128;
+  const AtdHeads<GQA> hd(h, h_kv);
+  const int ts = hd.ts;
   const int dots = h * ATT_D128;
   const uint64_t seed = rng_seed(salt, state);
   const float inv_keep = 1.f / keep;
   const unsigned keep16 = keep_to_16(keep);
 
-  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D128;
-  const ushort_t* kbase = qbase + (size_t)h * ATT_D128;
-  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D128;
+  const ushort_t* tokb = qkv + (size_t)b * S * ts;
+  const ushort_t* qbase = tokb + (size_t)hh * ATT_D128;
+  const ushort_t* kbase = tokb + (size_t)hd.kcol(hh / hd.G) * ATT_D128;
+  const ushort_t* vbase = tokb + (size_t)hd.vcol(hh / hd.G) * ATT_D128;
   const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D128;
   const ushort_t* obase = out + ((size_t)b * S * h + hh) * ATT_D128;
   float* mk = (float*)lds_at(lds, ATD_MASK_OFF);
@@ -399,19 +433,25 @@ ATD_KERNEL void attn_d128_bwd_dq_kernel(
 // bits (att_drop_bits_lds_long, 64 rows) @32K + 768: 34560 B.
 // CAUSAL: key block kb begins with query chunk kb, its diagonal chunk, and in
 // it wave w begins with tile w.
+// GQA: one block per (b, K/V head g, 64-key block), grid B * h_kv * ceil(S/64).
+// The wave's K and V fragments are loaded once and the block takes the walk
+// above once per query head of the group, g*G .. g*G + G-1, into the same
+// dK^T and dV^T: one fp32 sum over the group, one rounding, one store, no
+// atomics and no partials. G times the work in a block over G times fewer
+// blocks; the LDS and the registers are those of the one-head walk.
 #define ATD_Q_OFF KR_IMG0_OFF
 #define ATD_DO_OFF KR_IMG1_OFF
 #define ATD_STAT_OFF KR_AUX_OFF
 #define ATD_BITS_OFF (KR_AUX_OFF + 768)
 #define ATD_DKV_LDS (KR_AUX_OFF + 768 + 1024)
 
-template <bool HAS_MASK, bool CAUSAL>
+template <bool HAS_MASK, bool CAUSAL, bool GQA>
 ATD_KERNEL3 void attn_d128_bwd_dkv_kernel(
     const ushort_t* __restrict__ qkv, const ushort_t* __restrict__ dout,
     const ushort_t* __restrict__ mask, const float* __restrict__ m_io,
     const float* __restrict__ l_io, const float* __restrict__ dot_in,
     ushort_t* __restrict__ dqkv, int B, int S, int h, float scale, float keep,
-    uint64_t salt, const unsigned long long* __restrict__ state) {
+    uint64_t salt, const unsigned long long* __restrict__ state, int h_kv) {
   static_assert(!CAUSAL || !HAS_MASK, "causal mode takes no additive mask");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
@@ -420,20 +460,20 @@ ATD_KERNEL3 void attn_d128_bwd_dkv_kernel(
   const int lm = l & 15;
   const int lg = l >> 4;
   const int QB = (S + ATD_C - 1) / ATD_C;
-  const int bh = blockIdx.x / QB;
+  const AtdHeads<GQA> hd(h, h_kv);
+  const int bg = blockIdx.x / QB;  // b * h_kv + g
   const int kb = blockIdx.x % QB;
-  const int b = bh / h;
-  const int hh = bh % h;
-  const int ts = 3 * h * ATT_D128;
+  const int b = bg / hd.hkv;
+  const int g = bg % hd.hkv;
+  const int ts = hd.ts;
   const int dots = h * ATT_D128;
   const uint64_t seed = rng_seed(salt, state);
   const float inv_keep = 1.f / keep;
   const unsigned keep16 = keep_to_16(keep);
 
-  const ushort_t* qbase = qkv + (size_t)b * S * ts + (size_t)hh * ATT_D128;
-  const ushort_t* kbase = qbase + (size_t)h * ATT_D128;
-  const ushort_t* vbase = qbase + (size_t)2 * h * ATT_D128;
-  const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D128;
+  const ushort_t* tokb = qkv + (size_t)b * S * ts;
+  const ushort_t* kbase = tokb + (size_t)hd.kcol(g) * ATT_D128;
+  const ushort_t* vbase = tokb + (size_t)hd.vcol(g) * ATT_D128;
   float* st = (float*)lds_at(lds, ATD_STAT_OFF);
   unsigned char* bits = (unsigned char*)lds_at(lds, ATD_BITS_OFF);
 
@@ -457,147 +497,177 @@ ATD_KERNEL3 void attn_d128_bwd_dkv_kernel(
   f32x4 kacc[8], vacc[8];
   att_zero(kacc);
   att_zero(vacc);
+  // The group's G query heads one after the other (MHA: the one head g), each
+  // with its own walk over the query chunks; kacc and vacc run through all
+  // G * (QB - qc0) visits, so dK and dV of the shared head are summed in fp32
+  // and rounded once. Head, bh and the two base pointers come from the block
+  // index and the loop counter: scalars.
 #pragma clang loop unroll(disable)
-  for (int qch = qc0; qch < QB; ++qch) {
-    const int q0 = qch * ATD_C;
-    const int nq = S - q0 < ATD_C ? S - q0 : ATD_C;
-    const int NT = (nq + 15) / 16;
-    const int NP = (nq + 31) / 32;
-    if (qch != qc0) __syncthreads();  // the one barrier before LDS is reused
-    att_glds_rows128(qbase, ts, q0, NP * 32, S, lds, ATD_Q_OFF, tid);
-    att_glds_rows128(dobase, dots, q0, NP * 32, S, lds, ATD_DO_OFF, tid);
-    // rows >= S: 1/l = 0 and a false valid flag null P, dot = 0 keeps dS finite
-    if (tid < ATD_C) {
-      const int row = q0 + tid;
-      const bool live = row < S;
-      st[tid] = live ? m_io[(size_t)bh * S + row] : 0.f;
-      st[ATD_C + tid] = live ? 1.f / l_io[(size_t)bh * S + row] : 0.f;
-      st[2 * ATD_C + tid] = live ? dot_in[(size_t)bh * S + row] : 0.f;
-    }
-    if (keep < 1.f)
-      att_drop_bits_lds_long(bits, seed, bh, S, kb, q0, NP * 32, keep16, tid);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (!active) continue;
-    int lmc, lgc;
-    atd_chunk_lanes(lmc, lgc, lm, lg);
-    // CAUSAL: in the diagonal chunk the wave starts at its own tile (0 in
-    // every later chunk); wave-uniform, no barrier below
-    const int tw0 = CAUSAL && ktok_base > q0 ? (ktok_base - q0) >> 4 : 0;
+  for (int j = 0; j < hd.G; ++j) {
+    const int hh = g * hd.G + j;
+    const int bh = b * h + hh;  // the query head's: statistics, dot, dropout
+    const ushort_t* qbase = tokb + (size_t)hh * ATT_D128;
+    const ushort_t* dobase = dout + ((size_t)b * S * h + hh) * ATT_D128;
+#pragma clang loop unroll(disable)
+    for (int qch = qc0; qch < QB; ++qch) {
+      const int q0 = qch * ATD_C;
+      const int nq = S - q0 < ATD_C ? S - q0 : ATD_C;
+      const int NT = (nq + 15) / 16;
+      const int NP = (nq + 31) / 32;
+      // the one barrier before LDS is reused, on every visit but the block's
+      // first: the first chunk of head j + 1 overwrites what the last chunk of
+      // head j is still being read from. Waves without keys (!active) skip the
+      // work below and take every barrier of every head.
+      if (j != 0 || qch != qc0) __syncthreads();
+      att_glds_rows128(qbase, ts, q0, NP * 32, S, lds, ATD_Q_OFF, tid);
+      att_glds_rows128(dobase, dots, q0, NP * 32, S, lds, ATD_DO_OFF, tid);
+      // rows >= S: 1/l = 0 and a false valid flag null P, dot = 0 keeps dS finite
+      if (tid < ATD_C) {
+        const int row = q0 + tid;
+        const bool live = row < S;
+        st[tid] = live ? m_io[(size_t)bh * S + row] : 0.f;
+        st[ATD_C + tid] = live ? 1.f / l_io[(size_t)bh * S + row] : 0.f;
+        st[2 * ATD_C + tid] = live ? dot_in[(size_t)bh * S + row] : 0.f;
+      }
+      if (keep < 1.f)
+        att_drop_bits_lds_long(bits, seed, bh, S, kb, q0, NP * 32, keep16, tid);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (!active) continue;
+      int lmc, lgc;
+      atd_chunk_lanes(lmc, lgc, lm, lg);
+      // CAUSAL: in the diagonal chunk the wave starts at its own tile (0 in
+      // every later chunk); wave-uniform, no barrier below
+      const int tw0 = CAUSAL && ktok_base > q0 ? (ktok_base - q0) >> 4 : 0;
 
 #pragma unroll
-    for (int qp = 0; qp < 2; ++qp) {
-      if (qp >= NP) continue;
-      if constexpr (CAUSAL) if (qp < tw0 >> 1) continue;
-      f32x4 pd[2], ds[2];
-      att_zero(pd);
-      att_zero(ds);
-      // Q K^T and dO V^T: the images are the A side here, the wave's K and V
-      // fragments the B side, so a lane holds queries qt*16 + lg*4 + r
-      // against ITS key
-      att_score_tile_t128(pd, bk, lds, ATD_Q_OFF, 2 * qp, tw0, NT, lmc, lgc);
-      att_score_tile_t128(ds, bv, lds, ATD_DO_OFF, 2 * qp, tw0, NT, lmc, lgc);
+      for (int qp = 0; qp < 2; ++qp) {
+        if (qp >= NP) continue;
+        if constexpr (CAUSAL) if (qp < tw0 >> 1) continue;
+        f32x4 pd[2], ds[2];
+        att_zero(pd);
+        att_zero(ds);
+        // Q K^T and dO V^T: the images are the A side here, the wave's K and V
+        // fragments the B side, so a lane holds queries qt*16 + lg*4 + r
+        // against ITS key
+        att_score_tile_t128(pd, bk, lds, ATD_Q_OFF, 2 * qp, tw0, NT, lmc, lgc);
+        att_score_tile_t128(ds, bv, lds, ATD_DO_OFF, 2 * qp, tw0, NT, lmc, lgc);
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int qt = 2 * qp + t;
-        if (qt >= NT) continue;
-        if constexpr (CAUSAL) if (qt < tw0) continue;
-        const f32x4 m4 = *(const f32x4*)(st + qt * 16 + lgc * 4);
-        const f32x4 il4 = *(const f32x4*)(st + ATD_C + qt * 16 + lgc * 4);
-        const f32x4 dot4 = *(const f32x4*)(st + 2 * ATD_C + qt * 16 + lgc * 4);
-        unsigned kbits = 0xFFFFFFFFu;
-        if (keep < 1.f)
-          kbits = *(const unsigned*)(bits + ((qt * 4 + lgc) * 16 + lmc) * 4);
+        for (int t = 0; t < 2; ++t) {
+          const int qt = 2 * qp + t;
+          if (qt >= NT) continue;
+          if constexpr (CAUSAL) if (qt < tw0) continue;
+          const f32x4 m4 = *(const f32x4*)(st + qt * 16 + lgc * 4);
+          const f32x4 il4 = *(const f32x4*)(st + ATD_C + qt * 16 + lgc * 4);
+          const f32x4 dot4 = *(const f32x4*)(st + 2 * ATD_C + qt * 16 + lgc * 4);
+          unsigned kbits = 0xFFFFFFFFu;
+          if (keep < 1.f)
+            kbits = *(const unsigned*)(bits + ((qt * 4 + lgc) * 16 + lmc) * 4);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qq = q0 + qt * 16 + lg * 4 + r;
-          // the lane's token is the key here: the triangle compare turns round
-          const float mvr = (CAUSAL && qq < key) ? -3.0e38f : mv;
-          const float p = att_prob(pd[t][r], scale, mvr, m4[r], il4[r],
-                                   qq < S && key < S);
-          const bool kbit = (kbits >> (8 * r + w)) & 1u;
-          // Pd without its 1/keep, which dV^T takes at the end (as the
-          // forward's O^T does)
-          float pdv = p, dp = ds[t][r];
-          if (keep < 1.f) {
-            pdv = kbit ? p : 0.f;
-            dp = kbit ? dp * inv_keep : 0.f;
+          for (int r = 0; r < 4; ++r) {
+            const int qq = q0 + qt * 16 + lg * 4 + r;
+            // the lane's token is the key here: the triangle compare turns round
+            const float mvr = (CAUSAL && qq < key) ? -3.0e38f : mv;
+            const float p = att_prob(pd[t][r], scale, mvr, m4[r], il4[r],
+                                     qq < S && key < S);
+            const bool kbit = (kbits >> (8 * r + w)) & 1u;
+            // Pd without its 1/keep, which dV^T takes at the end (as the
+            // forward's O^T does)
+            float pdv = p, dp = ds[t][r];
+            if (keep < 1.f) {
+              pdv = kbit ? p : 0.f;
+              dp = kbit ? dp * inv_keep : 0.f;
+            }
+            pd[t][r] = pdv;
+            ds[t][r] = scale * p * (dp - dot4[r]);
           }
-          pd[t][r] = pdv;
-          ds[t][r] = scale * p * (dp - dot4[r]);
         }
-      }
-      const bf16x8 bpd = att_pack_dpair(pd[0], pd[1]);
-      const bf16x8 bds = att_pack_dpair(ds[0], ds[1]);
+        const bf16x8 bpd = att_pack_dpair(pd[0], pd[1]);
+        const bf16x8 bds = att_pack_dpair(ds[0], ds[1]);
 #pragma unroll
-      for (int ct = 0; ct < 8; ++ct) {
-        const bf16x8 adot = abf_tr_rows128_2(lds, ATD_DO_OFF, qp * 32 + lgc * 4,
-                                             qp * 32 + 16 + lgc * 4, ct * 4, lmc);
-        vacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adot, bpd, vacc[ct], 0, 0, 0);
-        const bf16x8 aqt = abf_tr_rows128_2(lds, ATD_Q_OFF, qp * 32 + lgc * 4,
-                                            qp * 32 + 16 + lgc * 4, ct * 4, lmc);
-        kacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aqt, bds, kacc[ct], 0, 0, 0);
+        for (int ct = 0; ct < 8; ++ct) {
+          const bf16x8 adot = abf_tr_rows128_2(lds, ATD_DO_OFF, qp * 32 + lgc * 4,
+                                               qp * 32 + 16 + lgc * 4, ct * 4, lmc);
+          vacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adot, bpd, vacc[ct], 0, 0, 0);
+          const bf16x8 aqt = abf_tr_rows128_2(lds, ATD_Q_OFF, qp * 32 + lgc * 4,
+                                              qp * 32 + 16 + lgc * 4, ct * 4, lmc);
+          kacc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aqt, bds, kacc[ct], 0, 0, 0);
+        }
       }
     }
   }
   if (!active) return;
 #pragma unroll
   for (int ct = 0; ct < 8; ++ct) vacc[ct] *= inv_keep;
-  ushort_t* dk = dqkv + (size_t)b * S * ts + (size_t)(h + hh) * ATT_D128;
-  ushort_t* dv = dqkv + (size_t)b * S * ts + (size_t)(2 * h + hh) * ATT_D128;
+  // stored once, at the K/V head's own columns
+  ushort_t* dk = dqkv + (size_t)b * S * ts + (size_t)hd.kcol(g) * ATT_D128;
+  ushort_t* dv = dqkv + (size_t)b * S * ts + (size_t)hd.vcol(g) * ATT_D128;
   att_store_cols16_d128(dk, ts, kacc, ktok_base, S, lm, lg);
   att_store_cols16_d128(dv, ts, vacc, ktok_base, S, lm, lg);
 }
 
 // ---------------------------------------------------------------------------
 // Entry points: d = 128 and 1 <= S <= 4096; argument lists as their
-// sky_attn_long_* counterparts, the causal pair without ids and bounds.
-static bool atd_shape_ok(int64_t S, int64_t d, bool causal) {
+// sky_attn_long_* counterparts, the causal pair without ids and bounds. The
+// sky_attn_d128_gqa_* forms take h_kv after h and the packed layout
+// [B, S, h + 2*h_kv, 128], 1 <= h_kv, h % h_kv == 0; out, m, l and dot are
+// indexed by the query head as in the multi-head forms.
+template <bool GQA>
+static bool atd_shape_ok(int64_t S, int64_t h, int64_t h_kv, int64_t d,
+                         bool causal) {
+  if (GQA && (h_kv < 1 || h % h_kv != 0)) return false;
   return d == ATT_D128 && S >= (causal ? 2 : 1) && S <= ATD_SMAX;
 }
-static dim3 atd_grid(int64_t B, int64_t S, int64_t h) {
-  return dim3((unsigned)(B * h * ((S + ATD_C - 1) / ATD_C)));
+// heads = h (forward, dQ: a block per query head) or h_kv (the GQA dK/dV)
+static dim3 atd_grid(int64_t B, int64_t S, int64_t heads) {
+  return dim3((unsigned)(B * heads * ((S + ATD_C - 1) / ATD_C)));
 }
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool GQA>
 static int atd_fwd(uint64_t stream, uint64_t qkv, uint64_t mask, uint64_t out,
                    uint64_t m, uint64_t lsum, int64_t B, int64_t S, int64_t h,
-                   int64_t d, float scale, float keep, uint64_t salt,
-                   uint64_t state) {
-  if (!atd_shape_ok(S, d, CAUSAL) || qkv == 0 || out == 0 || m == 0 || lsum == 0)
+                   int64_t h_kv, int64_t d, float scale, float keep,
+                   uint64_t salt, uint64_t state) {
+  if (!atd_shape_ok<GQA>(S, h, h_kv, d, CAUSAL) || qkv == 0 || out == 0 ||
+      m == 0 || lsum == 0)
     return (int)hipErrorInvalidValue;
-  ATT_LAUNCH_HM(!CAUSAL && mask != 0, (attn_d128_fwd_kernel<HM && !CAUSAL, CAUSAL>),
+  ATT_LAUNCH_HM(!CAUSAL && mask != 0,
+                (attn_d128_fwd_kernel<HM && !CAUSAL, CAUSAL, GQA>),
                 atd_grid(B, S, h), ATD_FWD_LDS, (hipStream_t)stream,
                 (const ushort_t*)qkv, (const ushort_t*)mask, (ushort_t*)out,
                 (float*)m, (float*)lsum, (int)B, (int)S, (int)h, scale, keep,
-                salt, (const unsigned long long*)state);
+                salt, (const unsigned long long*)state, (int)h_kv);
   LAUNCH_CHECK();
   return 0;
 }
 
 // dQ + dot, then dK/dV. out: the forward's output [B,S,h,128]; dot: fp32
 // [B*h*S], written by the dQ kernel and read by the dK/dV kernel.
-template <bool CAUSAL>
+template <bool CAUSAL, bool GQA>
 static int atd_bwd(uint64_t stream, uint64_t qkv, uint64_t dout, uint64_t out,
                    uint64_t mask, uint64_t m, uint64_t lsum, uint64_t dot,
-                   uint64_t dqkv, int64_t B, int64_t S, int64_t h, int64_t d,
-                   float scale, float keep, uint64_t salt, uint64_t state) {
-  if (!atd_shape_ok(S, d, CAUSAL) || qkv == 0 || dout == 0 || out == 0 ||
-      m == 0 || lsum == 0 || dot == 0 || dqkv == 0)
+                   uint64_t dqkv, int64_t B, int64_t S, int64_t h,
+                   int64_t h_kv, int64_t d, float scale, float keep,
+                   uint64_t salt, uint64_t state) {
+  if (!atd_shape_ok<GQA>(S, h, h_kv, d, CAUSAL) || qkv == 0 || dout == 0 ||
+      out == 0 || m == 0 || lsum == 0 || dot == 0 || dqkv == 0)
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  ATT_LAUNCH_HM(!CAUSAL && mask != 0, (attn_d128_bwd_dq_kernel<HM && !CAUSAL, CAUSAL>),
+  ATT_LAUNCH_HM(!CAUSAL && mask != 0,
+                (attn_d128_bwd_dq_kernel<HM && !CAUSAL, CAUSAL, GQA>),
                 atd_grid(B, S, h), ATD_FWD_LDS, s, (const ushort_t*)qkv,
                 (const ushort_t*)dout, (const ushort_t*)out,
                 (const ushort_t*)mask, (const float*)m, (const float*)lsum,
                 (float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h, scale,
-                keep, salt, (const unsigned long long*)state);
-  ATT_LAUNCH_HM(!CAUSAL && mask != 0, (attn_d128_bwd_dkv_kernel<HM && !CAUSAL, CAUSAL>),
-                atd_grid(B, S, h), ATD_DKV_LDS, s, (const ushort_t*)qkv,
-                (const ushort_t*)dout, (const ushort_t*)mask, (const float*)m,
-                (const float*)lsum, (const float*)dot, (ushort_t*)dqkv, (int)B,
-                (int)S, (int)h, scale, keep, salt,
-                (const unsigned long long*)state);
+                keep, salt, (const unsigned long long*)state, (int)h_kv);
+  ATT_LAUNCH_HM(!CAUSAL && mask != 0,
+                (attn_d128_bwd_dkv_kernel<HM && !CAUSAL, CAUSAL, GQA>),
+                atd_grid(B, S, GQA ? h_kv : h), ATD_DKV_LDS, s,
+                (const ushort_t*)qkv, (const ushort_t*)dout,
+                (const ushort_t*)mask, (const float*)m, (const float*)lsum,
+                (const float*)dot, (ushort_t*)dqkv, (int)B, (int)S, (int)h,
+                scale, keep, salt, (const unsigned long long*)state,
+                (int)h_kv);
   LAUNCH_CHECK();
   return 0;
 }
@@ -607,8 +677,8 @@ SKY_EXPORT int sky_attn_d128_fwd(uint64_t stream, uint64_t qkv, uint64_t mask,
                                  int64_t B, int64_t S, int64_t h, int64_t d,
                                  float scale, float keep, uint64_t salt,
                                  uint64_t state) {
-  return atd_fwd<false>(stream, qkv, mask, out, m, lsum, B, S, h, d, scale,
-                        keep, salt, state);
+  return atd_fwd<false, false>(stream, qkv, mask, out, m, lsum, B, S, h, h, d,
+                               scale, keep, salt, state);
 }
 
 SKY_EXPORT int sky_attn_d128_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
@@ -617,8 +687,8 @@ SKY_EXPORT int sky_attn_d128_bwd(uint64_t stream, uint64_t qkv, uint64_t dout,
                                  int64_t B, int64_t S, int64_t h, int64_t d,
                                  float scale, float keep, uint64_t salt,
                                  uint64_t state) {
-  return atd_bwd<false>(stream, qkv, dout, out, mask, m, lsum, dot, dqkv, B, S,
-                        h, d, scale, keep, salt, state);
+  return atd_bwd<false, false>(stream, qkv, dout, out, mask, m, lsum, dot,
+                               dqkv, B, S, h, h, d, scale, keep, salt, state);
 }
 
 // The causal forms (q attends k iff k <= q), 2 <= S <= 4096: no mask, no ids.
@@ -627,8 +697,8 @@ SKY_EXPORT int sky_attn_d128_causal_fwd(uint64_t stream, uint64_t qkv,
                                         int64_t B, int64_t S, int64_t h,
                                         int64_t d, float scale, float keep,
                                         uint64_t salt, uint64_t state) {
-  return atd_fwd<true>(stream, qkv, 0, out, m, lsum, B, S, h, d, scale, keep,
-                       salt, state);
+  return atd_fwd<true, false>(stream, qkv, 0, out, m, lsum, B, S, h, h, d,
+                              scale, keep, salt, state);
 }
 
 SKY_EXPORT int sky_attn_d128_causal_bwd(uint64_t stream, uint64_t qkv,
@@ -638,6 +708,51 @@ SKY_EXPORT int sky_attn_d128_causal_bwd(uint64_t stream, uint64_t qkv,
                                         int64_t h, int64_t d, float scale,
                                         float keep, uint64_t salt,
                                         uint64_t state) {
-  return atd_bwd<true>(stream, qkv, dout, out, 0, m, lsum, dot, dqkv, B, S, h,
-                       d, scale, keep, salt, state);
+  return atd_bwd<true, false>(stream, qkv, dout, out, 0, m, lsum, dot, dqkv, B,
+                              S, h, h, d, scale, keep, salt, state);
 }
+
+// Grouped-query forms: the four above with h_kv after h.
+SKY_EXPORT int sky_attn_d128_gqa_fwd(uint64_t stream, uint64_t qkv,
+                                     uint64_t mask, uint64_t out, uint64_t m,
+                                     uint64_t lsum, int64_t B, int64_t S,
+                                     int64_t h, int64_t h_kv, int64_t d,
+                                     float scale, float keep, uint64_t salt,
+                                     uint64_t state) {
+  return atd_fwd<false, true>(stream, qkv, mask, out, m, lsum, B, S, h, h_kv,
+                              d, scale, keep, salt, state);
+}
+
+SKY_EXPORT int sky_attn_d128_gqa_bwd(uint64_t stream, uint64_t qkv,
+                                     uint64_t dout, uint64_t out, uint64_t mask,
+                                     uint64_t m, uint64_t lsum, uint64_t dot,
+                                     uint64_t dqkv, int64_t B, int64_t S,
+                                     int64_t h, int64_t h_kv, int64_t d,
+                                     float scale, float keep, uint64_t salt,
+                                     uint64_t state) {
+  return atd_bwd<false, true>(stream, qkv, dout, out, mask, m, lsum, dot, dqkv,
+                              B, S, h, h_kv, d, scale, keep, salt, state);
+}
+
+SKY_EXPORT int sky_attn_d128_gqa_causal_fwd(uint64_t stream, uint64_t qkv,
+                                            uint64_t out, uint64_t m,
+                                            uint64_t lsum, int64_t B, int64_t S,
+                                            int64_t h, int64_t h_kv, int64_t d,
+                                            float scale, float keep,
+                                            uint64_t salt, uint64_t state) {
+  return atd_fwd<true, true>(stream, qkv, 0, out, m, lsum, B, S, h, h_kv, d,
+                             scale, keep, salt, state);
+}
+
+SKY_EXPORT int sky_attn_d128_gqa_causal_bwd(uint64_t stream, uint64_t qkv,
+                                            uint64_t dout, uint64_t out,
+                                            uint64_t m, uint64_t lsum,
+                                            uint64_t dot, uint64_t dqkv,
+                                            int64_t B, int64_t S, int64_t h,
+                                            int64_t h_kv, int64_t d, float scale,
+                                            float keep, uint64_t salt,
+                                            uint64_t state) {
+  return atd_bwd<true, true>(stream, qkv, dout, out, 0, m, lsum, dot, dqkv, B,
+                             S, h, h_kv, d, scale, keep, salt, state);
+}
+

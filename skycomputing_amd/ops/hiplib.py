@@ -165,6 +165,12 @@ def _register_signatures(lib):
         # strm qkv out m l | B S h d scale keep salt state
         "sky_attn_d128_causal_bwd": [u64] * 8 + [i64, i64, i64, i64, f32, f32, u64, u64],
         # strm qkv dout out m l dot dqkv | B S h d scale keep salt state
+        # grouped-query forms of the four above: h_kv after h, qkv and dqkv
+        # packed [B, S, h + 2*h_kv, 128], h % h_kv == 0
+        "sky_attn_d128_gqa_fwd": [u64] * 6 + [i64, i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_d128_gqa_bwd": [u64] * 9 + [i64, i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_d128_gqa_causal_fwd": [u64] * 5 + [i64, i64, i64, i64, i64, f32, f32, u64, u64],
+        "sky_attn_d128_gqa_causal_bwd": [u64] * 8 + [i64, i64, i64, i64, i64, f32, f32, u64, u64],
         "sky_layernorm_bwd_parts": [u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, i64, i64, i32, f32, u64, u64, u64, u64, u64],
         # sky_layernorm_bwd_xsum's arguments (dxsum 0 = the two-sum
         # sky_layernorm_bwd) + job; job.nv == 0 afterwards: nothing pending
